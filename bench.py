@@ -7,11 +7,15 @@ via torch.distributed.run): one process per GPU, each rank rasterizes its own sy
 (seed = rank) -- the product's one-chunk-per-GPU sharding, no data-path collective -- and
 `value` is the aggregate Mpix/s over all ranks (weak scaling).
 
-Prints ONE JSON line on rank 0.  Extras: "roofline" for the dominant kernel (algorithmic bytes
-per launch from SURVEY.md 8(d) / its HIP-event-measured average duration on the rasterizer's
-stream), "stages_ms" for every kernel, "cpu_baseline" (the C oracle, timed on the host cores on
-full-size fwd+bwd frames, rank 0 at N=1 only) and "cpu_baseline_torch" (the naive PyTorch-CPU
-splat of SURVEY.md 8(d) on config 1).
+Prints ONE JSON line on rank 0.  A plain run does only what the headline figure needs: set-up,
+warm-up, the timed steps, the line (metric, value, unit, ms_per_step, ...).  --dump-outputs DIR also
+writes what the last timed step returned (the forward's outputs and the inputs' gradients) as
+DIR/<name>.npy.  Everything else is behind --full: "roofline" for the dominant kernel (algorithmic
+bytes per launch from SURVEY.md 8(d) / its HIP-event-measured average duration on the rasterizer's
+stream), "stages_ms" for every kernel, the clock under load, the train-step / config 3 / 4 / 5 /
+street-frame / debug-mode legs, "cpu_baseline" (the C oracle, timed on the host cores on full-size
+fwd+bwd frames, rank 0 at N=1 only), "cpu_baseline_torch" (the naive PyTorch-CPU splat of SURVEY.md
+8(d) on config 1) and "psnr_vs_oracle".
 """
 from __future__ import annotations
 
@@ -41,7 +45,15 @@ def parse():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--sh-degree", type=int, default=3)
-    ap.add_argument("--profile-steps", type=int, default=5, help="extra steps with per-stage HIP events")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: the per-stage / roofline / clock diagnostics of "
+                         "the metric and the secondary legs (train step, configs 3-5, street frame, debug mode, CPU "
+                         "baselines, PSNR against the oracle); the --no-* / --metric-only switches select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (color, radii, invdepth and "
+                         "the gradients of the six inputs) as DIR/<name>.npy (float32; at most 64 MB in all: an array "
+                         "too large for its share is a fixed, seeded sample of its elements)")
+    ap.add_argument("--profile-steps", type=int, default=5, help="extra steps with per-stage HIP events (--full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--diag", action="store_true", help="print synced per-step fwd/bwd wall times to stderr")
     ap.add_argument("--train-steps", type=int, default=20, help="timed train-step harness iterations (0 = skip)")
@@ -54,8 +66,8 @@ def parse():
     ap.add_argument("--no-config4", action="store_true",
                     help="skip config 4 (500k-Gaussian chunk per rank, seed = chunk id: fwd+bwd and train step)")
     ap.add_argument("--metric-only", action="store_true",
-                    help="only the metric line's own work (profiling runs): no train step, configs 4/5, street "
-                         "frame or CPU baselines")
+                    help="with --full: only the metric line's own work and diagnostics (profiling runs): no train "
+                         "step, configs 4/5, street frame or CPU baselines")
     ap.add_argument("--c5-leaves", type=int, default=37_500_000, help="leaves of the config-5 tree (~4/3 as many nodes)")
     ap.add_argument("--c5-tau", type=float, default=15.0,
                     help="render_hierarchy.py tau in pixels (its default list: 0, 3, 6, 15)")
@@ -693,7 +705,10 @@ def rasterizer_for(s, W, H, deg, dev, debug=False):
     return rs, GaussianRasterizer(rs)
 
 
-def fwd_bwd_step(raster, inp, gcol, ginv):
+def fwd_bwd_step(raster, inp, gcol, ginv, keep=None):
+    """The timed step.  keep (a dict): the same step, which also leaves what the caller receives from
+    it -- the forward's outputs; the gradients stay on the inputs -- in `keep` (--dump-outputs: the
+    last timed step only, so the other steps hold no reference to their outputs, as without it)."""
     import torch
     leaves = list(inp.values())
 
@@ -702,8 +717,52 @@ def fwd_bwd_step(raster, inp, gcol, ginv):
             v.grad = None
         color, radii, invd = raster(**inp)
         torch.autograd.backward([color, invd], [gcol, ginv])
+        if keep is not None:
+            keep.update(color=color, radii=radii, invdepth=invd)
         return radii
     return step
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # of the 64 MB --dump-outputs may write (the .npy headers are ~128 B each)
+DUMP_SEED = 20240229
+
+
+def dump_plan(sizes, budget=DUMP_BUDGET_BYTES, itemsize=4):
+    """How many elements of each array --dump-outputs writes: {name: n_elements} -> {name: n_kept}.
+    The budget is shared evenly; an array smaller than its share is written whole and leaves the rest
+    of its share to the others (smallest first), an array larger than its share is sampled down to it."""
+    left, plan = budget // itemsize, {}
+    order = sorted(sizes, key=lambda k: (sizes[k], k))
+    for i, k in enumerate(order):
+        plan[k] = min(sizes[k], left // (len(order) - i))
+        left -= plan[k]
+    return plan
+
+
+def dump_sample(name, n, k):
+    """The flat element indices of `name` that a dump keeps (sorted; None: all of them).  A function
+    of the name, the array's size and the sample's size only, so two builds given the same arguments
+    write the same elements."""
+    if k >= n:
+        return None
+    import zlib
+    rng = np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode())])
+    return np.sort(rng.choice(n, size=k, replace=False))
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` ({name: tensor}) as path/<name>.npy in float32 -- whole (its own shape)
+    or the 1-D sample of dump_plan / dump_sample.  Returns what was written, for the line."""
+    os.makedirs(path, exist_ok=True)
+    plan = dump_plan({k: int(v.numel()) for k, v in arrays.items()})
+    done = {}
+    for name, t in arrays.items():
+        a = t.detach().to("cpu").numpy()
+        idx = dump_sample(name, a.size, plan[name])
+        a = a.astype(np.float32) if idx is None else a.reshape(-1)[idx].astype(np.float32)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        done[name] = {"shape": list(t.shape), "written": int(a.size), "sampled": idx is not None}
+    return done
 
 
 @contextlib.contextmanager
@@ -729,9 +788,10 @@ def settle():
     gc.collect()
 
 
-def timed(step, steps, warmup, ranks, per_step=None, host=None, per_call=None):
+def timed(step, steps, warmup, ranks, per_step=None, host=None, per_call=None, last_step=None):
     """W untimed steps, then exactly `steps` steps bracketed by barrier + synchronize on both sides;
-    the MAX over ranks of the elapsed seconds.  per_step (a list): receives each timed step's device
+    the MAX over ranks of the elapsed seconds.  last_step: the callable of the last timed step (the
+    same step, keeping its outputs: fwd_bwd_step's `keep`).  per_step (a list): receives each timed step's device
     duration in ms -- HIP events recorded on the current stream between consecutive steps (no
     synchronisation inside the timed region).  host (a dict): the host's side of the same steps --
     the time each step() call took to return (perf_counter, ms) and the part of it the forward spent
@@ -746,6 +806,9 @@ def timed(step, steps, warmup, ranks, per_step=None, host=None, per_call=None):
     torch.cuda.synchronize()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)] if per_step is not None else None
     ht = [0.0] * (steps + 1)
+    fns = [step] * steps
+    if last_step is not None and steps > 0:
+        fns[-1] = last_step
     with quiet_gc():
         k0 = _C.forward_stats()["k_wait_ns"] if host is not None else 0
         t0 = time.perf_counter()
@@ -753,7 +816,7 @@ def timed(step, steps, warmup, ranks, per_step=None, host=None, per_call=None):
             ev[0].record()
         ht[0] = time.perf_counter()
         for i in range(steps):
-            step()
+            fns[i]()
             ht[i + 1] = time.perf_counter()
             if ev is not None:
                 ev[i + 1].record()
@@ -1075,11 +1138,91 @@ def coarse_debug(a, dev):
     return out
 
 
+def metric_diagnostics(a, out, diag, detail, step, probe, rs, inp, dev, bwd_seg, fwd_seg, world):
+    """--full: the metric's diagnostics that take runs of their own, after the timed steps -- the clock
+    under load, the per-stage times, the frame's workload statistics and the rooflines built on them.
+    Adds to the line's `out` (config, roofline), to its trailing `diag` and to `detail`."""
+    import torch
+    P, W, H, deg = a.gaussians, a.width, a.height, a.sh_degree
+
+    # the clock under the bench's load: sampled over ~400 more (untimed) steps
+    def burst():
+        for _ in range(400):
+            step()
+        torch.cuda.synchronize()
+    clk_load = probe.sample_while(burst)
+
+    # per-stage device time with HIP events on the rasterizer's stream (separate, untimed steps)
+    stages = stage_profile(step, a.profile_steps)
+
+    # workload statistics for the algorithmic-bytes model (P1 measured: gsr_frame_stats)
+    wl = frame_workload(rs, inp, W, H, deg, dev)
+    K, Pv, P1 = wl["K"], wl["Pv"], wl["P1"]
+    # live rows (nonzero accumulated sums) of the frame: the rows whose means3D gradient is nonzero
+    # after the last step
+    g3 = inp["means3D"].grad
+    Pl = int((g3 != 0).any(dim=1).sum().item()) if g3 is not None else None
+    T = ((W + 15) // 16) * ((H + 15) // 16)
+    npix = W * H
+    abytes = algorithmic_bytes(P, Pv, K, T, npix, P1, M=inp["shs"].shape[1], Pl=Pl)
+    strict_8d = 44 * K + 24 * npix + 40 * Pv
+    serial_ms = sum(v for k, v in stages.items() if k not in OVERLAPPED_STAGES)
+    dom = max(stages, key=lambda k: stages[k]) if stages else "render_bwd"
+    dom_ms = stages.get(dom, 0.0)
+    achieved = abytes[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+    traffic, traffic_src, traffic_cur = latest_traffic(dom)
+    rp_ms = rocprof_ms(dom)
+    strict_frac = strict_8d / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if dom == "render_bwd" and dom_ms > 0 else None
+    zero_rows = (56 + 12 * inp["shs"].shape[1]) * P
+    out["config"] = {"workload": f"rasterizer fwd+bwd, {P} Gaussians, SH degree {deg}, {W}x{H}, do_depth",
+                     "gaussians": P, "width": W, "height": H, "sh_degree": deg, "visible": Pv, "tile_instances": K,
+                     "level1_entries": P1, "max_sb_list": wl["max_sb_list"],
+                     "tb_split_items": wl["tb_split_items"], "live_rows": Pl, "tiles": T, "bwd_segment": bwd_seg,
+                     "fwd_segment": fwd_seg, "parallelism": f"chunk-per-gpu x{world}"}
+    # frac: SURVEY.md 8(d)'s algorithmic bytes of the dominant kernel (render_bwd: 44 K + 24 Npix +
+    # 40 Pv) / its HIP-event time measured here; frac_rocprof: the same bytes / the average duration
+    # in the committed rocprofv3 summary of these kernel sources (profiles/, null when no summary
+    # of the current sources is committed); frac_with_zero_rows: also counting the dense zero
+    # gradient rows render_bwd's waves write (8(d) books them under preprocess-bwd)
+    out["roofline"] = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                       "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                       "algorithmic_bytes": abytes[dom], "avg_ms": round(dom_ms, 5),
+                       "traffic_source": traffic_src, "profile_is_current": traffic_cur, "rocprof_avg_ms": rp_ms,
+                       "frac_rocprof": round(abytes[dom] / (rp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if rp_ms else None,
+                       "kernel_source_sha": kernel_source_sha(),
+                       "frac_strict_8d": round(strict_frac, 5) if strict_frac is not None else None,
+                       "frac_with_zero_rows": round((abytes[dom] + zero_rows) / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                       if dom == "render_bwd" and dom_ms > 0 else None}
+    first = {
+        "valu_roofline": [{k_: r[k_] for k_ in ("kernel", "achieved", "unit", "frac_of_sustained",
+                                                 "valu_instr_per_launch", "avg_ms", "rocprof_avg_ms")}
+                          for r in (valu_roofline(k, stages.get(k)) for k in ("render_bwd", "render_fwd")) if r],
+        "stage_bytes": {k: int(v) for k, v in abytes.items()},
+        # stages on the main stream (sh_color overlaps the sort / binning on a side stream)
+        "pipeline_roofline": {"algorithmic_bytes": sum(abytes.values()),
+                              "frac": round(sum(abytes.values()) / (serial_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                              if serial_ms > 0 else None},
+        "stages_ms": {k: round(v, 5) for k, v in stages.items()},
+    }
+    rest = dict(diag)
+    diag.clear()
+    diag.update(first)
+    diag.update(rest)  # the line's order as before: the rooflines and stages, then the timed steps' by-products
+    clk = diag["gpu_clock"]
+    src = clk.pop("source")
+    del clk["error"]
+    clk.update({"under_load_median_mhz": (clk_load or {}).get("current_gfxclk_median"),
+                "under_load_power_w": (clk_load or {}).get("current_socket_power_median"),
+                "under_load_hotspot_c_max": (clk_load or {}).get("temperature_hotspot_max"),
+                "source": src, "error": probe.err})
+    detail["gpu_clock"]["under_load"] = clk_load
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a))
-    if a.metric_only:
+    if a.metric_only or not a.full:  # a plain run: the headline figure only, no secondary leg
         a.train_steps, a.no_config5, a.no_street, a.no_config4, a.no_cpu_baseline = 0, True, True, True, True
         a.no_coarse_debug = a.no_config3 = True
     import torch
@@ -1159,43 +1302,26 @@ def main():
     pw["gfxclk_at_timed_start"] = (clk_before or {}).get("current_gfxclk")
     # the timed region carries no per-step event records: each is a marker packet on the stream, and
     # a marker costs ~7 us of idle between the kernels around it (tools/kstamp.py, r06e)
-    elapsed = timed(step, a.steps, a.warmup, ranks, host=host_side, per_call=per_step)
+    kept = {} if a.dump_outputs else None
+    last = fwd_bwd_step(raster, inp, gcol, ginv, keep=kept) if kept is not None else None
+    elapsed = timed(step, a.steps, a.warmup, ranks, host=host_side, per_call=per_step, last_step=last)
     clk_after = probe.read()
-
-    # the clock under the bench's load: sampled over ~400 more (untimed) steps
-    def burst():
-        for _ in range(400):
-            step()
-        torch.cuda.synchronize()
-    clk_load = probe.sample_while(burst)
-
-    # per-stage device time with HIP events on the rasterizer's stream (separate, untimed steps)
-    stages = stage_profile(step, a.profile_steps)
-
-    # workload statistics for the algorithmic-bytes model (P1 measured: gsr_frame_stats)
-    wl = frame_workload(rs, inp, W, H, deg, dev)
-    K, Pv, P1 = wl["K"], wl["Pv"], wl["P1"]
-    # live rows (nonzero accumulated sums) of the frame: the rows whose means3D gradient is nonzero
-    # after the last step
-    g3 = inp["means3D"].grad
-    Pl = int((g3 != 0).any(dim=1).sum().item()) if g3 is not None else None
     T = ((W + 15) // 16) * ((H + 15) // 16)
     npix = W * H
-    abytes = algorithmic_bytes(P, Pv, K, T, npix, P1, M=inp["shs"].shape[1], Pl=Pl)
-    strict_8d = 44 * K + 24 * npix + 40 * Pv
-    serial_ms = sum(v for k, v in stages.items() if k not in OVERLAPPED_STAGES)
-    dom = max(stages, key=lambda k: stages[k]) if stages else "render_bwd"
-    dom_ms = stages.get(dom, 0.0)
-    achieved = abytes[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-    traffic, traffic_src, traffic_cur = latest_traffic(dom)
-    rp_ms = rocprof_ms(dom)
-
     ms_per_step = elapsed / a.steps * 1e3
     value = world * npix * a.steps / elapsed / 1e6
-    strict_frac = strict_8d / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if dom == "render_bwd" and dom_ms > 0 else None
-    zero_rows = (56 + 12 * inp["shs"].shape[1]) * P
+    dumped = None
+    if kept and rank == 0:  # what the last timed step returned: its outputs and the inputs' gradients
+        log("writing the last timed step's outputs")
+        arrays = dict(kept)
+        arrays.update({"grad_" + k_: v_.grad for k_, v_ in inp.items() if v_.grad is not None})
+        dumped = dump_outputs(a.dump_outputs, arrays)
+        del arrays
+    if kept is not None:
+        kept.clear()
+    del last
     out = {
-        "metric": "fwd+bwd Mpix/s at 1080p (1M Gaussians)",  # + "train_step" ms below
+        "metric": "fwd+bwd Mpix/s at 1080p (1M Gaussians)",  # + "train_step" ms below (--full)
         "value": round(value, 3),
         "unit": "Mpix/s",
         "n_gpus": world,
@@ -1208,47 +1334,24 @@ def main():
         "dtype": "f32",
         "data": "synthetic (seeded Gaussians in the frustum, SURVEY.md 8(d); one chunk per rank, seed = rank)",
         "config": {"workload": f"rasterizer fwd+bwd, {P} Gaussians, SH degree {deg}, {W}x{H}, do_depth",
-                   "gaussians": P, "width": W, "height": H, "sh_degree": deg, "visible": Pv, "tile_instances": K,
-                   "level1_entries": P1, "max_sb_list": wl["max_sb_list"],
-                   "tb_split_items": wl["tb_split_items"], "live_rows": Pl, "tiles": T, "bwd_segment": bwd_seg, "fwd_segment": fwd_seg,
-                   "parallelism": f"chunk-per-gpu x{world}"},
-        # frac: SURVEY.md 8(d)'s algorithmic bytes of the dominant kernel (render_bwd: 44 K + 24 Npix +
-        # 40 Pv) / its HIP-event time measured here; frac_rocprof: the same bytes / the average duration
-        # in the committed rocprofv3 summary of these kernel sources (profiles/, null when no summary
-        # of the current sources is committed); frac_with_zero_rows: also counting the dense zero
-        # gradient rows render_bwd's waves write (8(d) books them under preprocess-bwd)
-        "roofline": {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                     "algorithmic_bytes": abytes[dom], "avg_ms": round(dom_ms, 5),
-                     "traffic_source": traffic_src, "profile_is_current": traffic_cur, "rocprof_avg_ms": rp_ms,
-                     "frac_rocprof": round(abytes[dom] / (rp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if rp_ms else None,
-                     "kernel_source_sha": kernel_source_sha(),
-                     "frac_strict_8d": round(strict_frac, 5) if strict_frac is not None else None,
-                     "frac_with_zero_rows": round((abytes[dom] + zero_rows) / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-                     if dom == "render_bwd" and dom_ms > 0 else None},
+                   "gaussians": P, "width": W, "height": H, "sh_degree": deg, "tiles": T, "bwd_segment": bwd_seg,
+                   "fwd_segment": fwd_seg, "parallelism": f"chunk-per-gpu x{world}"},
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    # by-products of the timed steps themselves (no run of their own)
     diag = {
-        "valu_roofline": [{k_: r[k_] for k_ in ("kernel", "achieved", "unit", "frac_of_sustained",
-                                                 "valu_instr_per_launch", "avg_ms", "rocprof_avg_ms")}
-                          for r in (valu_roofline(k, stages.get(k)) for k in ("render_bwd", "render_fwd")) if r],
-        "stage_bytes": {k: int(v) for k, v in abytes.items()},
-        # stages on the main stream (sh_color overlaps the sort / binning on a side stream)
-        "pipeline_roofline": {"algorithmic_bytes": sum(abytes.values()),
-                              "frac": round(sum(abytes.values()) / (serial_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-                              if serial_ms > 0 else None},
-        "stages_ms": {k: round(v, 5) for k, v in stages.items()},
         "step_dispersion": dispersion(per_step),
         "host_issue": host_side,
         "gpu_clock": {"idle_mhz": (clk_idle or {}).get("current_gfxclk"),
                       "timed_start_mhz": (clk_before or {}).get("current_gfxclk"),
                       "timed_end_mhz": (clk_after or {}).get("current_gfxclk"),
-                      "under_load_median_mhz": (clk_load or {}).get("current_gfxclk_median"),
-                      "under_load_power_w": (clk_load or {}).get("current_socket_power_median"),
-                      "under_load_hotspot_c_max": (clk_load or {}).get("temperature_hotspot_max"),
                       "source": "amdsmi GPU metrics", "error": probe.err},
         "prewarm": pw,
     }
-    detail = {"gpu_clock": {"idle": clk_idle, "before": clk_before, "after": clk_after, "under_load": clk_load}}
+    detail = {"gpu_clock": {"idle": clk_idle, "before": clk_before, "after": clk_after}}
+    if a.full:
+        metric_diagnostics(a, out, diag, detail, step, probe, rs, inp, dev, bwd_seg, fwd_seg, world)
     del step, raster
     if a.train_steps > 0:
         log("train step")

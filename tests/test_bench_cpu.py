@@ -51,6 +51,28 @@ def test_compact_legs_moves_descriptive_numbers():
     assert detail["moved"]["config3_proxy.variant.slowest3"] == [[1, 2.0]] and detail["moved"]["config5.nodes"] == 50
 
 
+def test_dump_plan_shares_the_budget():
+    """--dump-outputs: small arrays whole, the rest of the budget shared evenly among the large ones;
+    the metric's own arrays (1M Gaussians at 1080p) stay under 64 MB; the sample is a function of the
+    name and the sizes alone."""
+    import numpy as np
+
+    import bench
+    assert bench.dump_plan({"a": 10, "b": 5}) == {"a": 10, "b": 5}
+    assert bench.dump_plan({"a": 100, "b": 5, "c": 40}, budget=4 * 65) == {"b": 5, "c": 30, "a": 30}
+    P, npix = 1_000_000, 1920 * 1080
+    sizes = {"color": 3 * npix, "invdepth": npix, "radii": P, "grad_means3D": 3 * P, "grad_means2D": 3 * P,
+             "grad_opacities": P, "grad_shs": 48 * P, "grad_scales": 3 * P, "grad_rotations": 4 * P}
+    plan = bench.dump_plan(sizes)
+    assert all(0 < plan[k] <= sizes[k] for k in sizes) and plan["radii"] == P and plan["grad_shs"] < 48 * P
+    assert 4 * sum(plan.values()) + 128 * len(plan) <= 64_000_000
+    assert bench.dump_sample("x", 10, 10) is None
+    i = bench.dump_sample("grad_shs", 1000, 100)
+    assert i.shape == (100,) and np.all(np.diff(i) > 0) and 0 <= i[0] and i[-1] < 1000
+    assert np.array_equal(i, bench.dump_sample("grad_shs", 1000, 100))
+    assert not np.array_equal(i, bench.dump_sample("grad_scales", 1000, 100))
+
+
 def test_dispersion_of_step_times():
     import bench
     d = bench.dispersion([0.65, 0.66, 0.70, 0.64, 0.90])

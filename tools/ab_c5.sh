@@ -6,7 +6,7 @@
 set -u -o pipefail
 TAG=$1; R=$2; shift 2
 O=gpurun_out/$TAG; mkdir -p "$O"
-ARGS="--steps 20 --warmup 5 --train-steps 0 --no-street --no-config4 --no-coarse-debug --no-cpu-baseline --no-config3 --post-leaves 0"
+ARGS="--full --steps 20 --warmup 5 --train-steps 0 --no-street --no-config4 --no-coarse-debug --no-cpu-baseline --no-config3 --post-leaves 0"
 for r in $(seq 1 "$R"); do
   for v in "$@"; do
     envs=""; lib=$v

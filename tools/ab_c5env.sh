@@ -1,6 +1,6 @@
 set -u -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06zy; mkdir -p $O
-C5="--steps 3 --warmup 2 --train-steps 0 --no-config3 --no-street --no-config4 --no-coarse-debug --no-cpu-baseline --post-leaves 0 --prewarm-s 0"
+C5="--full --steps 3 --warmup 2 --train-steps 0 --no-config3 --no-street --no-config4 --no-coarse-debug --no-cpu-baseline --post-leaves 0 --prewarm-s 0"
 for round in 1 2; do
   for b in 0 192 232 256; do
     if [ $b = 0 ]; then unset GSR_COLOR_BIG_BLOCKS; else export GSR_COLOR_BIG_BLOCKS=$b; fi

@@ -2,7 +2,7 @@
 # bench.py's config-5 leg only -> gpurun_out/<AB_TAG>/c5ab.log (ms_per_frame, sh_color, split)
 set -u -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${AB_TAG:-r06zk}; mkdir -p $O
-C5="--steps 3 --warmup 2 --train-steps 0 --no-config3 --no-street --no-config4 --no-coarse-debug --no-cpu-baseline --post-leaves 0 --prewarm-s 0"
+C5="--full --steps 3 --warmup 2 --train-steps 0 --no-config3 --no-street --no-config4 --no-coarse-debug --no-cpu-baseline --post-leaves 0 --prewarm-s 0"
 for round in 1 2; do
   for L in default $(ls $R/vlibs/c5_*.so); do
     if [ $L = default ]; then unset GSR_LIBRARY; else export GSR_LIBRARY=$L; fi

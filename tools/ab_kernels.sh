@@ -6,7 +6,7 @@ set -uo pipefail
 TAG=${1:-abk}
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/abk_$TAG; mkdir -p "$OUT"
-ARGS="--steps 20 --warmup 5 --profile-steps 1 --metric-only"
+ARGS="--full --steps 20 --warmup 5 --profile-steps 1 --metric-only"
 # AB_SCRIPT / AB_ARGS: profile another program (e.g. tools/train_step_profile.py --steps 20)
 SCRIPT=${AB_SCRIPT:-bench.py}
 [ -n "${AB_ARGS:-}" ] && ARGS=$AB_ARGS

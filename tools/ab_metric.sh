@@ -8,9 +8,9 @@ for r in $(seq 1 "$R"); do
   for lib in "$@"; do
     n=$(basename "$lib" .so)
     if [ "$lib" = default ]; then
-      timeout -k 10 300 python3 bench.py --metric-only --steps 50 --warmup 10 > "$O/$n.$r.json" 2> "$O/$n.$r.err" || exit 1
+      timeout -k 10 300 python3 bench.py --full --metric-only --steps 50 --warmup 10 > "$O/$n.$r.json" 2> "$O/$n.$r.err" || exit 1
     else
-      GSR_LIBRARY=$lib timeout -k 10 300 python3 bench.py --metric-only --steps 50 --warmup 10 > "$O/$n.$r.json" 2> "$O/$n.$r.err" || exit 1
+      GSR_LIBRARY=$lib timeout -k 10 300 python3 bench.py --full --metric-only --steps 50 --warmup 10 > "$O/$n.$r.json" 2> "$O/$n.$r.err" || exit 1
     fi
   done
 done

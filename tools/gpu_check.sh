@@ -14,7 +14,7 @@ timeout -k 10 1000 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeo
 rc=$?
 tail -5 "$OUT/gputest.log"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest rc $rc: stopping"; exit $rc; fi
-timeout -k 10 600 python3 -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python3 -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 brc=$?
 tail -c 600 "$OUT/bench.json"
 echo "pytest rc $rc bench rc $brc"

@@ -6,7 +6,7 @@
 #   tests=<k expr>   the same, only the tests matching -k <k expr>
 #   smoke            __graft_entry__.smoke()                        -> smoke.log
 #   host             tools/host_overhead.py (host cost of the API step)
-#   metric           bench.py --metric-only (the headline line only) -> metric.json
+#   metric           bench.py --full --metric-only (the headline line and its diagnostics) -> metric.json
 #   bench            the full default bench line                    -> bench.json
 #   driver           exactly the driver's command, `python3 bench.py --gpus 1 --steps 20 --warmup 5`
 #                    (its long diagnostics via GSR_BENCH_DETAIL_OUT)  -> driver.json, driver_detail.json
@@ -18,8 +18,8 @@ set -u -o pipefail
 TAG=${1:?tag}; shift
 O=gpurun_out/$TAG
 mkdir -p "$O"
-C3="--steps 5 --warmup 2 --train-steps 0 --no-config5 --no-street --no-config4 --no-coarse-debug --no-cpu-baseline --post-leaves 0"
-C5="--steps 3 --warmup 2 --train-steps 0 --no-config3 --no-street --no-config4 --no-coarse-debug --no-cpu-baseline --post-leaves 0 --prewarm-s 0"
+C3="--full --steps 5 --warmup 2 --train-steps 0 --no-config5 --no-street --no-config4 --no-coarse-debug --no-cpu-baseline --post-leaves 0"
+C5="--full --steps 3 --warmup 2 --train-steps 0 --no-config3 --no-street --no-config4 --no-coarse-debug --no-cpu-baseline --post-leaves 0 --prewarm-s 0"
 for st in "$@"; do
     echo "== $st" >&2
     case "$st" in
@@ -27,8 +27,8 @@ for st in "$@"; do
         tests=*) timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "${st#tests=}" > "$O/gputest.log" 2>&1 ;;
         smoke) timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 ;;
         host) timeout -k 10 300 python3 -u tools/host_overhead.py > "$O/host.log" 2>&1 ;;
-        metric) timeout -k 10 300 python3 -u bench.py --metric-only > "$O/metric.json" 2> "$O/metric.err" ;;
-        bench) timeout -k 10 900 python3 -u bench.py > "$O/bench.json" 2> "$O/bench.err" ;;
+        metric) timeout -k 10 300 python3 -u bench.py --full --metric-only > "$O/metric.json" 2> "$O/metric.err" ;;
+        bench) timeout -k 10 900 python3 -u bench.py --full > "$O/bench.json" 2> "$O/bench.err" ;;
         driver) GSR_BENCH_DETAIL_OUT="$O/driver_detail.json" timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 \
                     > "$O/driver.json" 2> "$O/driver.err" ;;
         profile) bash tools/profile_gpu.sh "$TAG" ;;
