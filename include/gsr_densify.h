@@ -5,8 +5,8 @@
  * Replaces GaussianModel.densify_and_prune (scene/gaussian_model.py:733-778) with
  * densify_and_clone (:708-731), densify_and_split (:672-706), prune_points (:588-603),
  * cat_tensors_to_optimizer (:605-644) and densification_postfix (:646-670), as train_single.py:197
- * calls it (gt_point_cloud_constraints off).  With P0 rows, g = xyz_gradient_accum (NaN -> 0),
- * op = sigmoid(opacity_raw), smax = max_k exp(scaling_raw[k]), rows r >= first_row only:
+ * calls it with gt_point_cloud_constraints off (on: gsr_densify_plan_gt, gsr_gtcloud.h).  With P0
+ * rows, g = xyz_gradient_accum (NaN -> 0), op = sigmoid(opacity_raw), smax = max_k exp(scaling_raw[k]), rows r >= first_row only:
  *
  *   clone  C_i = sqrt(g*g) * max_radii2D * op^0.2 >= max_grad  &&  op > 0.15  &&  smax <= max_scale
  *   split  S_i =        g  * max_radii2D * op^0.2 >= max_grad  &&  op > 0.15  &&  smax >  max_scale

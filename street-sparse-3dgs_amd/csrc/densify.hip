@@ -10,6 +10,11 @@
 //   apply: one launch over every (output row, element) of every group: copy, clone, or split
 //          child (xyz = R(q) (z * exp(s)) + xyz, scaling = log(exp(s) / 1.6)); Adam moments
 //          copied for old rows, zero for new ones
+//
+// gsr_densify_plan_gt (include/gsr_gtcloud.h) adds the ground-truth cloud's distance prune between
+// the predicates and the scan: the predicate pass also marks the rows D cannot matter on (split or
+// opacity-pruned), gtcloud.hip's query kernel runs on the others, and one pass clears the "old row
+// kept" / "clone kept" counters of the far rows and counts them.
 #include <cstring>
 #include <string>
 
@@ -17,6 +22,7 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_densify.h"
+#include "../../include/gsr_gtcloud.h"
 #include "gsr_launch.h"
 
 namespace gsr {
@@ -39,6 +45,7 @@ struct DensifyLayout {
     Cnt4 *flags, *pre, *tot;
     uint2 *map;
     void *tmp;
+    uint8_t *skip, *far;  // plan_gt: rows the distance test skips; its result
     size_t tmp_bytes, total;
 };
 
@@ -59,6 +66,8 @@ DensifyLayout densify_layout(char *base, int64_t P0) {
     rocprim::exclusive_scan(nullptr, bytes, (const Cnt4 *)nullptr, (Cnt4 *)nullptr, Cnt4{0, 0, 0, 0}, n, Cnt4Plus());
     L.tmp_bytes = bytes;
     L.tmp = take(bytes);
+    L.skip = reinterpret_cast<uint8_t *>(take(n));
+    L.far = reinterpret_cast<uint8_t *>(take(n));
     L.total = off;
     return L;
 }
@@ -67,7 +76,8 @@ __global__ __launch_bounds__(256) void densify_flags_kernel(int64_t P0, int64_t 
                                                             const float *__restrict__ maxr,
                                                             const float *__restrict__ o_raw,
                                                             const float *__restrict__ s_raw, float max_grad,
-                                                            float min_op, float max_scale, Cnt4 *__restrict__ flags) {
+                                                            float min_op, float max_scale, Cnt4 *__restrict__ flags,
+                                                            uint8_t *__restrict__ skip) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P0) return;
     float g = g_acc[i];
@@ -82,6 +92,33 @@ __global__ __launch_bounds__(256) void densify_flags_kernel(int64_t P0, int64_t 
     const bool prune = i >= first && op < min_op;
     flags[i] = Cnt4{(!split && !prune) ? 1u : 0u, (clone && !prune) ? 1u : 0u, split ? 1u : 0u,
                     (split && !prune) ? 1u : 0u};
+    if (skip) skip[i] = (split || prune) ? 1 : 0;
+}
+
+// plan_gt: rows the cloud's distance test found far lose their "old row kept" and "clone kept"
+// counters; counts[4] += rows removed (old + clones), counts[5] += of those the rows below `first`
+__global__ __launch_bounds__(256) void densify_gt_fix_kernel(int64_t P0, int64_t first,
+                                                             const uint8_t *__restrict__ far,
+                                                             Cnt4 *__restrict__ flags, int64_t *__restrict__ counts) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t removed = 0, fixed = 0;
+    if (i < P0 && far[i]) {
+        Cnt4 f = flags[i];
+        removed = f.a + f.b;
+        fixed = i < first ? f.a : 0u;
+        f.a = 0;
+        f.b = 0;
+        flags[i] = f;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        removed += __shfl_xor(removed, o);
+        fixed += __shfl_xor(fixed, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (removed) atomicAdd(reinterpret_cast<unsigned long long *>(counts + 4), (unsigned long long)removed);
+        if (fixed) atomicAdd(reinterpret_cast<unsigned long long *>(counts + 5), (unsigned long long)fixed);
+    }
 }
 
 __global__ void densify_totals_kernel(int64_t P0, const Cnt4 *__restrict__ flags, const Cnt4 *__restrict__ pre,
@@ -187,12 +224,14 @@ size_t gsr_densify_scratch_bytes(int64_t P0) {
     return densify_layout(nullptr, P0).total;
 }
 
-int gsr_densify_plan(int64_t P0, int64_t first_row, const float *grad_accum, const float *max_radii2D,
-                     const float *opacity_raw, const float *scaling_raw, float max_grad, float min_opacity,
-                     float max_scale, void *scratch, int64_t *counts, void *stream) {
+// gt != NULL: gsr_densify_plan_gt (counts has 6 entries, xyz the positions)
+static int densify_plan(const char *who, int64_t P0, int64_t first_row, const float *grad_accum,
+                        const float *max_radii2D, const float *opacity_raw, const float *scaling_raw, float max_grad,
+                        float min_opacity, float max_scale, void *scratch, int64_t *counts, void *stream,
+                        const GtGrid *gt, const float *xyz, float gt_T, float gt_reach) {
     if (P0 < 0 || P0 >= (1LL << 30) || first_row < 0 || !scratch || !counts ||
-        (P0 > 0 && (!grad_accum || !max_radii2D || !opacity_raw || !scaling_raw))) {
-        set_last_error("gsr_densify_plan: bad sizes (0 <= P0 < 2^30) or NULL pointer");
+        (P0 > 0 && (!grad_accum || !max_radii2D || !opacity_raw || !scaling_raw || (gt && !xyz)))) {
+        set_last_error(std::string(who) + ": bad sizes (0 <= P0 < 2^30) or NULL pointer");
         return GSR_ERR_INVALID_ARGUMENT;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -200,12 +239,18 @@ int gsr_densify_plan(int64_t P0, int64_t first_row, const float *grad_accum, con
     const unsigned blocks = (unsigned)((P0 + 255) / 256);
     if (P0 > 0) {
         hipLaunchKernelGGL(densify_flags_kernel, dim3(blocks), dim3(256), 0, s, P0, first_row, grad_accum, max_radii2D,
-                           opacity_raw, scaling_raw, max_grad, min_opacity, max_scale, L.flags);
+                           opacity_raw, scaling_raw, max_grad, min_opacity, max_scale, L.flags,
+                           gt ? L.skip : static_cast<uint8_t *>(nullptr));
+        if (gt) {
+            launch_gt_far_mask(P0, xyz, *gt, gt_T, gt_reach, L.skip, L.far, s);
+            hipLaunchKernelGGL(densify_gt_fix_kernel, dim3(blocks), dim3(256), 0, s, P0, first_row, L.far, L.flags,
+                               counts);
+        }
         size_t tb = L.tmp_bytes;
         const hipError_t e = rocprim::exclusive_scan(L.tmp, tb, L.flags, L.pre, Cnt4{0, 0, 0, 0}, (size_t)P0,
                                                      Cnt4Plus(), s);
         if (e != hipSuccess) {
-            set_last_error(std::string("gsr_densify_plan: scan: ") + hipGetErrorString(e));
+            set_last_error(std::string(who) + ": scan: " + hipGetErrorString(e));
             return GSR_ERR_DEVICE;
         }
     }
@@ -214,10 +259,36 @@ int gsr_densify_plan(int64_t P0, int64_t first_row, const float *grad_accum, con
         hipLaunchKernelGGL(densify_map_kernel, dim3(blocks), dim3(256), 0, s, P0, L.flags, L.pre, L.tot, L.map);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        set_last_error(std::string("gsr_densify_plan: ") + hipGetErrorString(e));
+        set_last_error(std::string(who) + ": " + hipGetErrorString(e));
         return GSR_ERR_DEVICE;
     }
     return GSR_OK;
+}
+
+int gsr_densify_plan(int64_t P0, int64_t first_row, const float *grad_accum, const float *max_radii2D,
+                     const float *opacity_raw, const float *scaling_raw, float max_grad, float min_opacity,
+                     float max_scale, void *scratch, int64_t *counts, void *stream) {
+    return densify_plan("gsr_densify_plan", P0, first_row, grad_accum, max_radii2D, opacity_raw, scaling_raw, max_grad,
+                        min_opacity, max_scale, scratch, counts, stream, nullptr, nullptr, 0.f, 0.f);
+}
+
+int gsr_densify_plan_gt(int64_t P0, int64_t first_row, const float *grad_accum, const float *max_radii2D,
+                        const float *opacity_raw, const float *scaling_raw, const float *xyz, float max_grad,
+                        float min_opacity, float max_scale, const gsr_gt_index *index, double thr, void *scratch,
+                        int64_t *counts, void *stream) {
+    GtGrid g;
+    float T, reach;
+    if (!gt_grid_of(index, &g) || !gt_thresholds(thr, &T, &reach) || !counts) {
+        set_last_error("gsr_densify_plan_gt: not an index, a bad threshold or NULL counts");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    const hipError_t e = hipMemsetAsync(counts + 4, 0, 2 * sizeof(int64_t), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) {
+        set_last_error(std::string("gsr_densify_plan_gt: ") + hipGetErrorString(e));
+        return GSR_ERR_DEVICE;
+    }
+    return densify_plan("gsr_densify_plan_gt", P0, first_row, grad_accum, max_radii2D, opacity_raw, scaling_raw,
+                        max_grad, min_opacity, max_scale, scratch, counts, stream, &g, xyz, T, reach);
 }
 
 int gsr_densify_apply(int64_t P0, int n_groups, const gsr_row_group *src, const gsr_row_group *dst, int xyz_group,

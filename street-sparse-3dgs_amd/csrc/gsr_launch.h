@@ -61,6 +61,33 @@ void launch_mark_visible(int P, const float *means3D, const float *view, uint8_t
 size_t sort_pairs_temp_bytes(size_t n, int end_bit);
 hipError_t sort_pairs(void *tmp, size_t tmp_bytes, const uint32_t *kin, uint32_t *kout, const uint32_t *vin,
                       uint32_t *vout, size_t n, int end_bit, hipStream_t s);
+// Stable sort of n (64-bit key, value) pairs over key bits [0, end_bit) (gtcloud.hip's cell keys).
+size_t sort_pairs64_temp_bytes(size_t n, int end_bit);
+hipError_t sort_pairs64(void *tmp, size_t tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint32_t *vin,
+                        uint32_t *vout, size_t n, int end_bit, hipStream_t s);
+// Runs of equal keys in a sorted array: each run's key and first position, and the number of runs.
+size_t key_runs_temp_bytes(size_t n);
+hipError_t key_runs(void *tmp, size_t tmp_bytes, const uint64_t *keys, size_t n, uint64_t *run_key,
+                    uint32_t *run_start, uint32_t *n_runs, hipStream_t s);
+
+// gtcloud.hip: what a query kernel needs of a gsr_gt_index (include/gsr_gtcloud.h)
+struct GtGrid {
+    const float4 *pts;          // the cloud in cell order (w unused)
+    const uint64_t *cell_key;   // ascending keys of the occupied cells
+    const uint32_t *cell_start; // n_cells + 1: first point of each cell, then G
+    uint32_t n_cells;
+    float lo[3], hi[3];         // the cloud's fp32 bounding box
+    float inv_h;
+    int32_t n[3];               // cells per axis
+};
+bool gt_grid_of(const void *index, GtGrid *out);  // false: NULL or not a live index
+// T: the largest fp32 <= thr^2 (thr a double); reach: an fp32 upper bound of the per-axis distance
+// of any point with d2 <= T.  false: thr not finite, <= 0 or thr^2 below the fp32 normal range
+bool gt_thresholds(double thr, float *T, float *reach);
+// out[i] = D_i (gsr_gtcloud.h) for rows with skip[i] == 0 (skip may be NULL), else 0
+void launch_gt_far_mask(int64_t P, const float *xyz, const GtGrid &g, float T, float reach, const uint8_t *skip,
+                        uint8_t *out, hipStream_t s);
+
 // dsort.hip: the stable (depth bits, id) order of the P Gaussians (gs.order), depth-ordered tile
 // rects (gs.drect, from gs.rect8), the Gaussian-major record offsets (rec.off) and
 // K = sum of tiles_touched, stored to *dsort_K_word and, when host_K != NULL, to that pinned

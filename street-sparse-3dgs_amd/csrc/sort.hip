@@ -39,4 +39,31 @@ hipError_t sort_pairs(void *tmp, size_t tmp_bytes, const uint32_t *kin, uint32_t
     return rocprim::radix_sort_pairs<OnesweepCfg>(tmp, tmp_bytes, kin, kout, vin, vout, n, 0, end_bit, s);
 }
 
+// 64-bit cell keys of the ground-truth cloud's grid (gtcloud.hip): once per cloud, default config
+size_t sort_pairs64_temp_bytes(size_t n, int end_bit) {
+    size_t bytes = 0;
+    rocprim::radix_sort_pairs(nullptr, bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr,
+                              (const uint32_t *)nullptr, (uint32_t *)nullptr, n > 0 ? n : 1, 0, end_bit);
+    return bytes;
+}
+
+hipError_t sort_pairs64(void *tmp, size_t tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint32_t *vin,
+                        uint32_t *vout, size_t n, int end_bit, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    return rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, 0, end_bit, s);
+}
+
+size_t key_runs_temp_bytes(size_t n) {
+    size_t bytes = 0;
+    rocprim::unique_by_key(nullptr, bytes, (const uint64_t *)nullptr, rocprim::counting_iterator<uint32_t>(0),
+                           (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, n > 0 ? n : 1);
+    return bytes;
+}
+
+hipError_t key_runs(void *tmp, size_t tmp_bytes, const uint64_t *keys, size_t n, uint64_t *run_key,
+                    uint32_t *run_start, uint32_t *n_runs, hipStream_t s) {
+    return rocprim::unique_by_key(tmp, tmp_bytes, keys, rocprim::counting_iterator<uint32_t>(0), run_key, run_start,
+                                  n_runs, n, rocprim::equal_to<uint64_t>(), s);
+}
+
 }  // namespace gsr

@@ -133,6 +133,17 @@ SIGNATURES = {
     "gsr_zero_grad_rows": (_i, [_i, ctypes.POINTER(_vp), ctypes.POINTER(_i64), _i64, _i64, _vp, _i64, _vp]),
 }
 
+# include/gsr_gtcloud.h (the ground-truth cloud constraint of densification); typed by load() like SIGNATURES
+_d = ctypes.c_double
+GT_SIGNATURES = {
+    "gsr_gt_index_create": (_vp, [_i64, _vp, _d, _vp]),
+    "gsr_gt_index_destroy": (None, [_vp]),
+    "gsr_gt_index_bounds": (_i, [_vp, ctypes.POINTER(_f)]),
+    "gsr_gt_index_info": (_i, [_vp, ctypes.POINTER(_i64), _i]),
+    "gsr_gt_far_mask": (_i, [_i64, _vp, _vp, _d, _vp, _vp, _vp]),
+    "gsr_densify_plan_gt": (_i, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _d, _vp, _vp, _vp]),
+}
+
 ABI_VERSION = 6
 _lib = None
 
@@ -154,7 +165,7 @@ def load(path: str = LIB_PATH):
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the host
         raise RasterizerLibraryError(f"failed to load {path}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(GT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

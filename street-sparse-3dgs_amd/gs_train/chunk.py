@@ -374,7 +374,8 @@ def street_scene(n_truth, length, device, seed=0, half_width=7.0, height=8.0, ca
 
 def street_chunk(step_cls=None, W=1536, H=1536, positions=48, faces=4, depth_only_every=4, n_truth=1_000_000,
                  n_init=300_000, skybox=10_000, n_scaffold=20_000, spacing=1.5, seed=0, device="cuda",
-                 iterations=30_000, lidar_keep=0.3, alpha=True):
+                 iterations=30_000, lidar_keep=0.3, alpha=True, gt_cloud_points=0, gt_threshold=0.05,
+                 gt_cloud_noise=0.01):
     """A synthetic Street-sparse chunk (the config-3 stand-in): `positions` camera stations along the
     street, `faces` 90-degree cube faces each (ss_utils/generate_colmap_calibration.py:476-479,572:
     W x H faces with f = W / 2), plus one depth-only view (a LiDAR-like sparse inverse-depth map,
@@ -386,7 +387,13 @@ def street_chunk(step_cls=None, W=1536, H=1536, positions=48, faces=4, depth_onl
     The initial Gaussians follow create_from_pcd with a scaffold_file (scene/gaussian_model.py:
     163-278): [skybox | coarse scaffold] rows first (scaffold_points = both, skybox_points the first
     ones), then `n_init` LiDAR-like points (truth surface points + 3 cm noise) with SH DC from their
-    colour, distCUDA2 scales, identity rotations and opacity 0.01.  Returns (step, info)."""
+    colour, distCUDA2 scales, identity rotations and opacity 0.01.
+
+    gt_cloud_points > 0 (off by default): the chunk also gets a ground-truth cloud of that many points
+    on the truth street's surfaces (gs_train.synthetic.street_cloud, noise gt_cloud_noise), indexed as
+    a gs_train.gtcloud.GtPointCloud with threshold gt_threshold and handed to the step, whose
+    densification then prunes against it (dataset.gt_point_cloud_constraints); info["gt_cloud"] is
+    the cloud and info["gt_points"] its (n, 3) float32 points.  Nothing else of the chunk changes.  Returns (step, info)."""
     from .harness import GaussianSet, TrainStep
     from simple_knn._C import distCUDA2
     step_cls = step_cls or TrainStep
@@ -463,11 +470,20 @@ def street_chunk(step_cls=None, W=1536, H=1536, positions=48, faces=4, depth_onl
     model = GaussianSet(m.cpu().numpy(), shs.cpu().numpy(), opac.cpu().numpy(), scales.cpu().numpy(),
                         rots.cpu().numpy(), n_images=n, sh_degree=0, spatial_lr_scale=extent, device=dev,
                         joined_features=getattr(step_cls, "JOINED_FEATURES", True))
+    extra = {}
+    if gt_cloud_points:
+        from .gtcloud import GtPointCloud
+        from .synthetic import street_cloud
+        gt_points = street_cloud(truth["means3D"].cpu().numpy(), int(gt_cloud_points), noise=gt_cloud_noise,
+                                 seed=seed + 13)
+        extra["gt_cloud"] = GtPointCloud(gt_points, threshold=gt_threshold, device=dev)
     ts = step_cls(model, cams, gts, W, H, cameras_extent=extent, mono_invdepths=monos, depth_masks=dmasks,
                   alpha_masks=amasks, skybox_points=skybox, scaffold_points=skybox + n_scaffold,
-                  iterations=iterations, depth_only=donly)
+                  iterations=iterations, depth_only=donly, **extra)
     info = dict(views=n, depth_only_views=int(sum(donly)), P_init=model.P, extent=extent, W=W, H=H,
-                truth=int(truth["means3D"].shape[0]))
+                truth=int(truth["means3D"].shape[0]), **extra)
+    if gt_cloud_points:
+        info["gt_points"] = gt_points
     return ts, info
 
 

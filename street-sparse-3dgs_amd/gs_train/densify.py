@@ -7,10 +7,12 @@ nonzero() (a host sync) and runs three indexed torch updates; here the radius te
 row on the device.
 
 densify_and_prune: GaussianModel.densify_and_prune (scene/gaussian_model.py:733-778, clone +
-split + opacity prune, gt_point_cloud_constraints off) as one planned gather over every
-parameter and Adam moment (include/gsr_densify.h): one host read of four counts, the split
-samples drawn exactly as the reference's torch.normal draws them, one launch writing the new
-arrays."""
+split + opacity prune) as one planned gather over every parameter and Adam moment
+(include/gsr_densify.h): one host read of four counts, the split samples drawn exactly as the
+reference's torch.normal draws them, one launch writing the new arrays.  With a ground-truth cloud
+(gs_train.gtcloud.GtPointCloud; the reference's gt_point_cloud_constraints) the plan also drops the
+old rows and clones farther than the cloud's threshold from every cloud point
+(include/gsr_gtcloud.h, compare_points_to_gt)."""
 from __future__ import annotations
 
 import torch
@@ -33,13 +35,17 @@ def add_densification_stats(radii: torch.Tensor, means2D_grad: torch.Tensor, max
 
 
 def densify_and_prune(g, optimizer, max_grad: float, min_opacity: float, extent: float, percent_dense: float,
-                      first_row: int = 0, normals: torch.Tensor = None) -> dict:
+                      first_row: int = 0, normals: torch.Tensor = None, gt_cloud=None) -> dict:
     """g: a joined-layout gs_train.harness.GaussianSet; optimizer: its gs_train.optim.Adam.  Replaces
     the parameters (and their optimizer state) with the densified / pruned rows and resets the
     densification statistics, as the reference does.  first_row: scaffold_points (rows never
     densified or pruned).  normals: the (2 n_split, 3) standard-normal draws behind the split
     samples, if given (parity tests inject the reference's own; a callable gets n_split and returns
-    them); drawn here otherwise.  Returns the plan's counts."""
+    them); drawn here otherwise.  gt_cloud: a gs_train.gtcloud.GtPointCloud turns the reference's
+    gt_point_cloud_constraints on: old rows and clones inside the cloud's XY bounds with no cloud
+    point within its threshold are dropped too -- rows below first_row included, as in the reference,
+    which clears only the opacity prune there -- and the returned dict also has gt_pruned (rows so
+    removed) and gt_pruned_fixed (of those, rows below first_row).  Returns the plan's counts."""
     from diff_gaussian_rasterization._lib import RowGroup
     if not getattr(g, "joined", False):
         raise ValueError("densify_and_prune works on the joined (P,16,3) SH layout")
@@ -51,12 +57,23 @@ def densify_and_prune(g, optimizer, max_grad: float, min_opacity: float, extent:
     L = lib()
     s = stream(dev)
     scratch = torch.empty(max(1, L.gsr_densify_scratch_bytes(P0)), dtype=torch.uint8, device=dev)
-    counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    counts = torch.zeros(4 if gt_cloud is None else 6, dtype=torch.int64, device=dev)
     acc = g.xyz_gradient_accum.reshape(-1).contiguous()
-    check(L.gsr_densify_plan(P0, int(first_row), ptr(acc), ptr(g.max_radii2D.contiguous()), ptr(g._opacity.detach()),
-                             ptr(g._scaling.detach()), float(max_grad), float(min_opacity),
-                             float(percent_dense * extent), ptr(scratch), ptr(counts), s), "gsr_densify_plan")
-    n_old, n_clone, n_split, total = (int(v) for v in counts.cpu())
+    if gt_cloud is None:
+        check(L.gsr_densify_plan(P0, int(first_row), ptr(acc), ptr(g.max_radii2D.contiguous()),
+                                 ptr(g._opacity.detach()), ptr(g._scaling.detach()), float(max_grad),
+                                 float(min_opacity), float(percent_dense * extent), ptr(scratch), ptr(counts), s),
+              "gsr_densify_plan")
+    else:
+        if gt_cloud.device != dev:
+            raise ValueError("gt_cloud: not on the model's device")
+        check(L.gsr_densify_plan_gt(P0, int(first_row), ptr(acc), ptr(g.max_radii2D.contiguous()),
+                                    ptr(g._opacity.detach()), ptr(g._scaling.detach()), ptr(g._xyz.detach()),
+                                    float(max_grad), float(min_opacity), float(percent_dense * extent),
+                                    gt_cloud.handle, float(gt_cloud.threshold), ptr(scratch), ptr(counts), s),
+              "gsr_densify_plan_gt")
+    host_counts = [int(v) for v in counts.cpu()]
+    n_old, n_clone, n_split, total = host_counts[:4]
     # the reference's torch.normal(mean=zeros, std=stds) draws normal_(0, 1) on a (2 n_split, 3)
     # tensor and scales it: the same generator stream
     if callable(normals):
@@ -98,4 +115,7 @@ def densify_and_prune(g, optimizer, max_grad: float, min_opacity: float, extent:
     g.xyz_gradient_accum = torch.zeros((total, 1), device=dev)
     g.denom = torch.zeros((total, 1), device=dev)
     g.max_radii2D = torch.zeros((total,), device=dev)
-    return dict(kept=n_old, cloned=n_clone, split=n_split, total=total)
+    out = dict(kept=n_old, cloned=n_clone, split=n_split, total=total)
+    if gt_cloud is not None:
+        out.update(gt_pruned=host_counts[4], gt_pruned_fixed=host_counts[5])
+    return out

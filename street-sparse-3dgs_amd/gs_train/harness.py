@@ -157,12 +157,16 @@ class TrainStep:
     scaffold (scene/gaussian_model.py:224-262, loaded with a scaffold_file), which the scale shrink
     leaves alone (train_single.py:239-240: violators[:scaffold_points] = False).  depth_only: per
     view, True for a depth-only view (its gts entry may be None; it needs a mono inverse-depth map);
-    dens_weight: additional_depth_maps_weight."""
+    dens_weight: additional_depth_maps_weight.  gt_cloud: a gs_train.gtcloud.GtPointCloud turns on
+    dataset.gt_point_cloud_constraints (train_single.py:197): densify_and_prune also drops the rows
+    farther than its threshold from the cloud."""
 
     def __init__(self, gaussians: GaussianSet, cameras, gts, W, H, cameras_extent=10.0, mono_invdepths=None,
                  depth_masks=None, alpha_masks=None, skybox_points=0, scaffold_points=0,
-                 iterations=LR["iterations"], depth_only=None, dens_weight=ADDITIONAL_DEPTH_MAPS_WEIGHT):
+                 iterations=LR["iterations"], depth_only=None, dens_weight=ADDITIONAL_DEPTH_MAPS_WEIGHT,
+                 gt_cloud=None):
         self.g = gaussians
+        self.gt_cloud = gt_cloud
         self.W, self.H = W, H
         self.extent = cameras_extent
         self.gts = gts
@@ -269,11 +273,12 @@ class TrainStep:
 
     # ---- the loop's events (gs_train.chunk.TrainChunk; train_single.py:196-201) ----
     def densify_and_prune(self, max_grad, min_opacity, percent_dense, normals=None):
-        """gaussians.densify_and_prune(max_grad, min_opacity, cameras_extent, False) on the device
-        (gs_train.densify).  normals: callable(n_split) -> the split draws, or None."""
+        """gaussians.densify_and_prune(max_grad, min_opacity, cameras_extent,
+        dataset.gt_point_cloud_constraints) on the device (gs_train.densify); the constraint is on
+        when the step has a gt_cloud.  normals: callable(n_split) -> the split draws, or None."""
         from .densify import densify_and_prune
         return densify_and_prune(self.g, self.optimizer, max_grad, min_opacity, self.extent, percent_dense,
-                                 first_row=self.scaffold, normals=normals)
+                                 first_row=self.scaffold, normals=normals, gt_cloud=self.gt_cloud)
 
     def reset_opacity(self):
         from .chunk import reset_opacity

@@ -227,3 +227,18 @@ def synthetic_lod_hierarchy(L, W, H, device, seed=0, branching=4, skybox=0, sh_d
 def tau_threshold(tau, tanfovx, W):
     """render_hierarchy.py:61: the target size for a tau (in pixels)."""
     return (2 * (tau + 0.5)) * tanfovx / (0.5 * W)
+
+
+def street_cloud(surface_points, n, noise=0.01, seed=0):
+    """A LiDAR-like ground-truth cloud for gs_train.chunk.street_chunk (its gt_cloud_points keyword):
+    `n` of the street's surface points (an (N, 3) array: the truth scene's Gaussian centres lie on
+    the road, the facades and the clutter boxes), drawn without replacement while N allows and with
+    replacement beyond, each moved by `noise` (metres, normal) as a scanner's range noise does.
+    Returns an (n, 3) float32 array; the same seed gives the same cloud."""
+    pts = np.asarray(surface_points, np.float32).reshape(-1, 3)
+    if pts.shape[0] < 1 or n < 1:
+        raise ValueError("street_cloud: needs at least one surface point and n >= 1")
+    rng = np.random.default_rng(seed)
+    idx = rng.permutation(pts.shape[0])[:n] if n <= pts.shape[0] else rng.integers(0, pts.shape[0], n)
+    out = pts[idx] + rng.normal(size=(n, 3)).astype(np.float32) * np.float32(noise)
+    return np.ascontiguousarray(out.astype(np.float32))
