@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 6
+#define GSR_ABI_VERSION 7
 
 typedef enum {
     GSR_OK = 0,
@@ -175,6 +175,12 @@ int gsr_set_fwd_segment(int L);
 /* The shortest tile list the forward split takes, process-wide: 0 (default) = 6 segments
  * (GSR_FSEG_FACTOR); otherwise max(len, L).  Returns the previous setting. */
 int gsr_set_fwd_split_min(int len);
+
+/* When the forward split's worker pool is launched, process-wide.  1 (default): ahead of tile_order,
+ * on a side stream, so its workgroups are resident before render_fwd's grid fills the CUs.  0: beside
+ * render_fwd.  The images are the same bits either way.  Returns the previous setting, or
+ * GSR_ERR_INVALID_ARGUMENT for any other value (ABI 7). */
+int gsr_set_fwd_early_workers(int enable);
 
 /* The forward-split workers' bounded spins, process-wide (for tests; 0 = the default): `ready` loop
  * trips (~256 clocks each) waiting for tile_order's release of the queue, after which a worker

@@ -68,6 +68,12 @@ int gsr_photo_loss_forward(const float *img, const float *gt, int C, int H, int 
 int gsr_photo_loss_backward(const float *img, const float *gt, const float *ssim_grad_map, int C, int H, int W,
                             double lambda_dssim, const float *dL_dloss, float *dL_dimg, void *stream);
 
+/* Which kernel forms the SSIM gradient field (gsr_l1_ssim_backward, the _with_map / photo-loss
+ * forwards and the native train step), process-wide.  0 (default): the streaming kernel.  1: the
+ * 64 x 16 tile kernel, the cross-check implementation the tests compare the streaming kernel
+ * against (same bits).  Returns the previous kernel, or GSR_ERR_INVALID_ARGUMENT (ABI 7). */
+int gsr_set_ssim_kernel(int kernel);
+
 /* One parameter group of the sparse Adam step: a (P, width) row-major parameter with its grad
  * and moment buffers.  step_size = lr / (1 - beta1^step) and bias_correction2_sqrt =
  * sqrt(1 - beta2^step) are computed by the host in double, exactly as OurAdam does. */
@@ -90,6 +96,14 @@ typedef struct {
  * relevance NULL: a dense step over every row (one launch; flag_scratch unused). */
 int gsr_sparse_adam_step(int n_groups, const gsr_adam_group *groups, int64_t P, const float *relevance,
                          double beta1, double beta2, double eps, int *flag_scratch, void *stream);
+
+/* Which kernel runs the Adam steps (gsr_sparse_adam_step and the native train step), process-wide;
+ * the updates are the same bits in every mode.  0 (default): flat runs for a dense step, the
+ * compacted list of relevant rows for a sparse step whose row (all groups' widths) fits one wave,
+ * row blocks otherwise.  1: the row-block kernel for every step.  2: the element-per-thread kernel
+ * (the native step's fused scale shrink and sparse gradient rows then fail with
+ * GSR_ERR_UNSUPPORTED).  Returns the previous kernel, or GSR_ERR_INVALID_ARGUMENT (ABI 7). */
+int gsr_set_adam_kernel(int kernel);
 
 /* out[c][p] = clamp(sum_k color[k][p] * E[k][c] + E[c][3], 0, 1) for the 3 planes of npix
  * pixels; E is the 3x4 exposure matrix (row-major, device). */
@@ -160,7 +174,7 @@ int gsr_depth_only_loss_backward(const float *invdepth, const float *mono_invdep
  * arithmetic of the entry points above and gsr_rasterize_forward_ex / _backward in the order
  * gs_train/harness.py TrainStep.step issues them (several fused into one launch), so its results
  * are those of the Python step (bit for bit in the deterministic backward mode).  The context owns every per-step
- * intermediate (rasterizer buffers, images, activated values and their gradients) in grow-only
+ * intermediate (rasterizer buffers, images, the activated values' gradients) in grow-only
  * device allocations reused across steps; the caller owns the parameters, their gradients
  * (overwritten each step), the Adam moments and the densification statistics.
  * Replaces the Python-driven step; none of the reference's files has a native executor. */
@@ -169,9 +183,9 @@ gsr_train_ctx *gsr_train_ctx_create(void);
 /* Waits for the last step's stream, then frees the context's device buffers. */
 void gsr_train_ctx_destroy(gsr_train_ctx *ctx);
 /* The context's buffer statistics: out[0] = buffer growths since creation (each re-allocates one
- * grow-only buffer 1/4 larger than asked; stream-ordered, hipFreeAsync / hipMallocAsync from the
- * device's default pool, unless GSR_STEP_SYNC_ALLOC=1), out[1] = bytes held, out[2] = 1 when the
- * growth is stream-ordered.  Returns the number of values written (<= n).  ABI 5. */
+ * grow-only buffer 1/4 larger than asked, in stream order: hipFreeAsync and an allocation from the
+ * context's own memory pool), out[1] = bytes held, out[2] = 1 (the growth is always stream-ordered).
+ * Returns the number of values written (<= n).  ABI 5. */
 int gsr_train_ctx_stats(const gsr_train_ctx *ctx, int64_t *out, int n);
 
 typedef struct {
@@ -221,6 +235,11 @@ typedef struct {
      * statistics and the optimizers and then takes no Gaussian Adam step (:190-201, :217, :225);
      * the caller runs those and the shrink itself (gsr_shrink_scales).  ABI 3. */
     int skip_gaussian_step;
+    /* Nonzero: the rasterizer backward writes every gradient row, as the Python-driven step does.
+     * 0 (default): the rows of Gaussians no pixel's backward reached (all-zero gradients, never
+     * relevant to the sparse Adam) are not written in xyz / features / scaling / rotation_grad.
+     * The parameters, moments and statistics after the step are the same either way.  ABI 7. */
+    int dense_rows;
 } gsr_train_step_args;
 
 /* *num_rendered receives the frame's K. */

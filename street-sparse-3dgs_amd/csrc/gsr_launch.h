@@ -146,7 +146,6 @@ struct ZeroRows {
     uint64_t n[kZeroArrays];
     uint64_t c4[kZeroArrays + 1];
     uint64_t per4;
-    uint32_t zfrom;    // workgroups below zfrom carry no zero rows (workgroup b >= zfrom: slice b - zfrom)
     uint32_t *stamps;  // != NULL: render_bwd stamps every staged Gaussian (live_stamp) with `stamp`
     uint32_t stamp;
 };
@@ -174,8 +173,6 @@ void launch_render_fwd_cleanup(const Camera &cam, const GeomState &gs, const Bin
 // the workers' spin limits (gsr_set_fwd_spin_limits) with the pinned host words
 FwdSpin fwd_spin(uint32_t *host_words);
 void set_fwd_spin_limits(uint32_t ready, uint32_t flag);
-// GSR_FWD_EARLY_WORKERS (default 1): launch_render_fwd_workers before tile_order; 0: beside render_fwd
-bool fwd_early_workers();
 // seg_len != 0: the backward's heavy tiles are cut into segments of seg_len list positions
 // (gsr_set_bwd_segment; the backward must get the value its forward was made with)
 void launch_render_bwd(const Camera &cam, const GeomState &gs, const BinningState &bs, const ImageState &is,
@@ -265,14 +262,13 @@ int step_loss_backward(const float *img, const float *gt, const float *gmap, con
                        double b1, double b2, double eps, hipStream_t s, bool gmap_is_photo = false);
 // activation backward + skybox lock + relevance flag + densification statistics.  sparse_rows:
 // the rasterizer backward wrote sparse rows (GaussianGrads): the scale / rotation gradients of
-// rows it did not write are neither read nor written.
-// scales / opac NULL: recomputed from the raw parameters (scaling_raw, opacity_raw) -- the raw mode
-int step_activate_backward(int64_t P, const float *rotation_raw, const float *scales, const float *opac,
-                           const float *d_scales, const float *d_rots, const float *d_opac, float *scaling_grad,
-                           float *rotation_grad, float *opacity_grad, int64_t skybox, int *flag, const int *radii,
-                           const float *d_means2D, float *max_radii2D, float *accum, float *denom, hipStream_t s,
-                           bool sparse_rows = false, const float *scaling_raw = nullptr,
-                           const float *opacity_raw = nullptr);
+// rows it did not write are neither read nor written.  The activations are recomputed from the raw
+// parameters (rotation_raw, scaling_raw, opacity_raw).
+int step_activate_backward(int64_t P, const float *rotation_raw, const float *d_scales, const float *d_rots,
+                           const float *d_opac, float *scaling_grad, float *rotation_grad, float *opacity_grad,
+                           int64_t skybox, int *flag, const int *radii, const float *d_means2D, float *max_radii2D,
+                           float *accum, float *denom, hipStream_t s, bool sparse_rows, const float *scaling_raw,
+                           const float *opacity_raw);
 
 // kernel stamps of each translation unit (GSR_KSTAMP builds; gsr_kstamp_read)
 int kstamp_read_preprocess(unsigned long long *out);

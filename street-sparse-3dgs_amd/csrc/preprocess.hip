@@ -411,15 +411,13 @@ void launch_preprocess(const GaussianInputs &in, const Camera &cam, const GeomSt
 #undef GSR_PRE_ARGS
 }
 
-// blocks < 0: a full grid of 4-wave blocks (52 KiB, three per CU), for a pass forked after the depth
-// sort beside the binning: config 5's 7.46M-row pass 1.16 -> 1.06 ms (r05f, vlibs cw4).  Beside the
-// sort itself they take the CUs its passes need (config 5: sort 0.36 -> 1.05 ms, r05g), so a pass
-// forked before the sort (blocks == 0) or a persistent grid (blocks > 0) runs 8-wave blocks.
+// blocks > 0: a persistent grid of that many blocks; 0: GSR_COLOR_BLOCKS (a full grid by default).
+// A full grid of 4-wave blocks (52 KiB, three per CU) was measured for a pass forked after the depth
+// sort beside the binning: config 5's 7.46M-row pass 1.16 -> 1.06 ms (r05f), but beside the sort
+// itself such blocks take the CUs its passes need (config 5: sort 0.36 -> 1.05 ms, r05g).
 void launch_preprocess_color(const GaussianInputs &in, const Camera &cam, const GeomState &gs, const int *radii,
                              hipStream_t s, int blocks) {
     if (in.P == 0) return;
-    const bool four = blocks < 0;
-    if (blocks < 0) blocks = 0;
     const int cap = blocks > 0 ? blocks : GSR_COLOR_BLOCKS;
     const auto go = [&](auto kw) {
         constexpr int kW = decltype(kw)::value, kT = kW * kWave;
@@ -432,8 +430,7 @@ void launch_preprocess_color(const GaussianInputs &in, const Camera &cam, const 
             hipLaunchKernelGGL((preprocess_color_kernel<false, kW>), dim3(grid), dim3(kT), 0, s, in.P, in.D,
                                in.means3D, in.shs, cam.campos, cam.view, radii, gs, nvb, in.cut);
     };
-    if (four && cap == 0) go(std::integral_constant<int, 4>{});
-    else if (in.cut.ri) go(std::integral_constant<int, GSR_COLOR_WAVES_CUT>{});
+    if (in.cut.ri) go(std::integral_constant<int, GSR_COLOR_WAVES_CUT>{});
     else go(std::integral_constant<int, kColorWaves>{});
 }
 

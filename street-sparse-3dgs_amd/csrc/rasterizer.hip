@@ -183,16 +183,6 @@ bool side_stream(hipStream_t main, hipStream_t *side, hipEvent_t *fork, hipEvent
     return true;
 }
 
-// tile_bin split of long superblock lists: the list length past which an SB is sliced, GSR_TB_SPLIT
-// or the environment's GSR_TB_SPLIT (measurement A/B; 0 = off)
-uint32_t tb_split_len() {
-    static const uint32_t len = [] {
-        const char *e = getenv("GSR_TB_SPLIT");
-        return e ? (uint32_t)std::max(0, atoi(e)) : (uint32_t)GSR_TB_SPLIT;
-    }();
-    return len;
-}
-
 // Joins the side stream into the main one when the forward leaves early (errors), so the
 // caller's buffers are never released under side-stream work.
 struct SideJoin {
@@ -203,38 +193,6 @@ struct SideJoin {
         if (pending) (void)hipStreamWaitEvent(s, join, 0);
     }
 };
-
-
-// Frames whose depth sort fills every CU (P above ~1M): the SH colour pass forks right after the
-// preprocess at full width instead of after the sort (GSR_COLOR_EARLY_BIG=0 for the A/B).
-// Measured on config 5 (7.46M rows, GSR_COLOR_FORK=0 variant, r05e): 3.73 -> 3.63 ms per frame.
-bool color_early_big() {
-    static const bool v = [] {
-        const char *e = std::getenv("GSR_COLOR_EARLY_BIG");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-// The same frames' colour pass as a persistent grid of this many blocks (GSR_COLOR_BIG_BLOCKS; 0 = a
-// full grid of 4-wave blocks), for the A/B of config 3's 20-30 ms stalls (a depth-sort or binning
-// kernel and the full-grid colour pass both stretched to the same end, r05f spikes.json)
-// A full-grid colour pass forked after the sort: 8-wave blocks (0, default) or 4-wave blocks
-// (GSR_COLOR_LATE_WAVES=4, -1; launch_preprocess_color).  Config 3 (r05h): 8 waves 55.8 s, 4 waves
-// 56.3 s -- the colour pass itself 0.224 -> 0.139 ms, but beside it bin_superblocks 0.153 -> 0.186 ms.
-int color_late_grid() {
-    static const int v = [] {
-        const char *e = std::getenv("GSR_COLOR_LATE_WAVES");
-        return e && std::atoi(e) == 4 ? -1 : 0;
-    }();
-    return v;
-}
-int color_big_blocks() {
-    static const int v = [] {
-        const char *e = std::getenv("GSR_COLOR_BIG_BLOCKS");
-        return e ? std::max(0, std::atoi(e)) : 0;
-    }();
-    return v;
-}
 
 int fail(int code, const std::string &msg) {
     g_err = msg;
@@ -590,6 +548,9 @@ std::atomic<uint32_t> g_bwd_seg{GSR_BWD_SEG_DEFAULT};
 #define GSR_FWD_SEG_DEFAULT 2048  // behind the split gate; config 3 (r05j/r05k): 4096 55.8-56.0 s, 2048 53.9 s, 1024 54.2-54.8 s
 #endif
 std::atomic<uint32_t> g_fwd_seg{GSR_FWD_SEG_DEFAULT};
+// gsr_set_fwd_early_workers: 1 = the forward segments' worker pool is launched ahead of tile_order,
+// 0 = beside render_fwd
+std::atomic<int> g_fwd_early_workers{1};
 std::mutex g_seg_mu;
 std::unordered_map<const void *, uint32_t> g_seg_of;
 // A forward made without segments (L = 0: switched off, or the 32-bit item-numbering guard) is
@@ -789,9 +750,10 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
                 // the sort fills the chip (large P).  Two rounds of it or more (config 5's 7.46M rows):
                 // the colour pass forks right after the preprocess, so it overlaps the sort as well
                 // as the binning (config 5 3.62 -> 3.51 ms, r05f); config 3's 3M-row frames measured
-                // no gain (55.0 vs 55.3 s), so they keep the fork after the sort
-                color_early = color_early_big() && dsort_blocks(P) >= 2 * device_cus();
-                color_blocks = color_big_blocks() ? color_big_blocks() : color_early ? 0 : color_late_grid();
+                // no gain (55.0 vs 55.3 s), so they keep the fork after the sort.  Either way a full
+                // grid of 8-wave blocks.
+                color_early = dsort_blocks(P) >= 2 * device_cus();
+                color_blocks = 0;
             }
         }
     }
@@ -942,7 +904,7 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
     bool joined = false;
     const uint32_t seg_req = need_bwd && bwd_segments_supported() ? g_bwd_seg.load(std::memory_order_relaxed) : 0u;
     uint32_t fseg_req = fwd_segments_supported() && !sb_order ? g_fwd_seg.load(std::memory_order_relaxed) : 0u;
-    uint32_t tb_req = tb_split_len();
+    uint32_t tb_req = GSR_TB_SPLIT;  // the list length past which tile_bin slices a superblock (0: off)
     // the split's minimum list length, read once per frame: tile_order's queue, render_fwd's skip test
     // and the gate must agree even if gsr_set_fwd_split_min runs meanwhile
     const uint32_t fseg_min = fseg_req ? fseg_min_len(fseg_req) : 0u;
@@ -1006,8 +968,8 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
         hipStream_t ws = s;
         hipEvent_t wf = nullptr, wj = nullptr;
         bool early = false;
-        if (fseg_used && !sb_order && fwd_early_workers() && !fwd_segments_in_kernel() &&
-            side_stream(s, &ws, &wf, &wj, 1) && ws != s) {
+        if (fseg_used && !sb_order && g_fwd_early_workers.load(std::memory_order_relaxed) &&
+            !fwd_segments_in_kernel() && side_stream(s, &ws, &wf, &wj, 1) && ws != s) {
             if (hipEventRecord(wf, s) != hipSuccess || hipStreamWaitEvent(ws, wf, 0) != hipSuccess ||
                 (split && !GSR_COLOR_SERIAL && !joined && hipStreamWaitEvent(ws, join, 0) != hipSuccess))
                 return fail(GSR_ERR_DEVICE, "side stream fork failed");
@@ -1263,6 +1225,11 @@ int gsr_set_fwd_segment(int L) {
     if (L > 0 && !fwd_segments_supported())
         return fail(GSR_ERR_UNSUPPORTED, "forward segments need the list-length launch order and the 1-row sub-block forward");
     return (int)g_fwd_seg.exchange((uint32_t)L);
+}
+
+int gsr_set_fwd_early_workers(int enable) {
+    if (enable < 0 || enable > 1) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_set_fwd_early_workers: enable 0 or 1");
+    return g_fwd_early_workers.exchange(enable);
 }
 
 int gsr_set_bwd_segment(int L) {

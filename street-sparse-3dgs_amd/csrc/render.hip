@@ -959,21 +959,6 @@ void launch_tile_order(const uint32_t *work, const uint2 *ranges, int T, int shi
                        host_tilelist, fwd_ready);
 }
 
-// the worker pool's size: kFwdPoolWorkers, or GSR_FWD_WORKERS from the environment (measurement A/B)
-static int fwd_workers() {
-    static const int n = [] {
-        const char *e = getenv("GSR_FWD_WORKERS");
-        const int v = e ? atoi(e) : 0;
-        return v > 0 ? v : kFwdPoolWorkers;
-    }();
-    return n;
-}
-
-bool fwd_early_workers() {  // read per frame, so a test can switch it
-    const char *e = getenv("GSR_FWD_EARLY_WORKERS");
-    return !(e && e[0] == '0');
-}
-
 static void launch_workers(const Camera &cam, const GeomState &gs, const BinningState &bs, const ImageState &is,
                            const float *bg, float *out_color, float *out_invdepth, bool need_bwd, uint32_t seg_len,
                            uint32_t fseg_len, hipStream_t ws, const uint32_t *ready, FwdSpin spin, int grid) {
@@ -990,7 +975,7 @@ void launch_render_fwd_workers(const Camera &cam, const GeomState &gs, const Bin
                                uint32_t fseg_len, hipStream_t ws, const uint32_t *ready, FwdSpin spin) {
     if (cam.gx * cam.gy == 0 || !fseg_len || GSR_FWD_SUB != 1 || GSR_FWD_SEG_INKERNEL) return;
     launch_workers(cam, gs, bs, is, bg, out_color, out_invdepth, need_bwd, seg_len, fseg_len, ws, ready, spin,
-                   fwd_workers());
+                   kFwdPoolWorkers);
 }
 
 // 64 workgroups: normally they find the queue drained (or take a straggler's last items); if the early
@@ -1026,7 +1011,7 @@ void launch_render_fwd(const Camera &cam, const GeomState &gs, const BinningStat
     const int grid = (sb_order ? sg.nsb << (2 * sg.shift) : T) + (GSR_FWD_SEG_INKERNEL && fseg_len ? kFwdWorkers : 0);
     if (fseg_len && !GSR_FWD_SEG_INKERNEL && !workers_launched)
         launch_workers(cam, gs, bs, is, bg, out_color, out_invdepth, need_bwd, seg_len, fseg_len,
-                       worker_stream ? worker_stream : s, nullptr, spin, fwd_workers());
+                       worker_stream ? worker_stream : s, nullptr, spin, kFwdPoolWorkers);
     // launch order: is.tile_ids (rasterizer.hip, by list length)
 #define GSR_FWD_LAUNCH(K, NT)                                                                                       \
     hipLaunchKernelGGL(K, dim3(grid), dim3(NT), 0, s, is.ranges, bs.point_list, cam.W, cam.H, cam.gx, gs.rec, bg,   \
@@ -1088,17 +1073,17 @@ __device__ __forceinline__ void bwd_gather(const GRec *__restrict__ rec, const u
 // preprocess_bwd no longer streams these bytes on its own
 __device__ __forceinline__ void bwd_zero_slice(const ZeroRows &zr) {
     const int lane = threadIdx.x;
-    if (!zr.per4 || blockIdx.x < zr.zfrom) return;
+    if (!zr.per4) return;
     {
         typedef float f4 __attribute__((ext_vector_type(4)));
-        const uint64_t q0 = (uint64_t)(blockIdx.x - zr.zfrom) * zr.per4, q1 = min(zr.c4[kZeroArrays], q0 + zr.per4);
+        const uint64_t q0 = (uint64_t)blockIdx.x * zr.per4, q1 = min(zr.c4[kZeroArrays], q0 + zr.per4);
         for (uint64_t q = q0 + (uint64_t)lane; q < q1; q += kWave) {
             int k = 0;
 #pragma unroll
             for (int a = 1; a < kZeroArrays; a++) k += q >= zr.c4[a];
             __builtin_nontemporal_store(f4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f4 *>(zr.p[k]) + (q - zr.c4[k]));
         }
-        if (blockIdx.x == zr.zfrom && lane < 4 * kZeroArrays) {  // the floats past each array's last whole float4
+        if (blockIdx.x == 0 && lane < 4 * kZeroArrays) {  // the floats past each array's last whole float4
             const int k = lane >> 2, t = lane & 3;
             const uint64_t e = 4 * (zr.c4[k + 1] - zr.c4[k]) + (uint64_t)t;
             if (e < zr.n[k]) __builtin_nontemporal_store(0.f, zr.p[k] + e);

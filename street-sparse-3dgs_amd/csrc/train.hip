@@ -15,6 +15,7 @@
 // updates them and scatters them back, one torch op at a time, after a host-synchronising
 // nonzero().  Here one launch walks all six groups' (param, grad, m, v) arrays once, testing
 // relevance (opacity grad != 0) per row on the device.
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -1097,7 +1098,7 @@ int flat_adam_runs(int n_groups, const gsr_adam_group *groups, int64_t P, FlatAd
 //                        192-B contiguous access per array, then the shrink of the row's scales.
 // With no relevant row (the dense fallback, OurAdam.py:214) the list pass is skipped and the row
 // kernel walks every row (the sparse-rows zero gradients of DenseRows applied).  Same per-element
-// arithmetic as adam_narrow (bits unchanged).  GSR_ADAM_ROWBLOCK=1: the row-block kernel (A/B).
+// arithmetic as adam_narrow (bits unchanged).  gsr_set_adam_kernel(1): the row-block kernel instead.
 constexpr int kAdamListMaxLanes = 64;
 __device__ __forceinline__ uint32_t lane_prefix_u64(uint64_t m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -1230,23 +1231,11 @@ __global__ __launch_bounds__(256) void adam_rowlist_kernel(AdamArgs a, AdamLaneM
     }
 }
 
-bool adam_rowblock() {  // read per call: A/B runs switch it
-    const char *e = std::getenv("GSR_ADAM_ROWBLOCK");
-    return e != nullptr && e[0] == '1';
-}
-
-// GSR_ADAM_DENSE_ROWS=1 sends a dense step through the row-block kernel instead (A/B).
-bool adam_dense_rows() {
-    const char *e = std::getenv("GSR_ADAM_DENSE_ROWS");
-    return e != nullptr && e[0] == '1';
-}
-
-// GSR_ADAM_ELEMENTWISE=1 selects the element-per-thread kernel (same bits; A/B test and
-// measurements).  Read per call so a test can switch it.
-bool adam_elementwise() {
-    const char *e = std::getenv("GSR_ADAM_ELEMENTWISE");
-    return e != nullptr && e[0] == '1';
-}
+// gsr_set_adam_kernel: 0 = flat runs for a dense step, the compacted row list for a sparse step whose
+// row fits one wave, row blocks otherwise; 1 = the row-block kernel for every step; 2 = the
+// element-per-thread kernel.  Same bits in every mode (tests/test_gpu_train.py).
+enum AdamKernel { kAdamAuto = 0, kAdamRowBlocks = 1, kAdamElementwise = 2 };
+std::atomic<int> g_adam_kernel{kAdamAuto};
 
 __global__ __launch_bounds__(256) void densify_stats_kernel(int64_t P, const int *__restrict__ radii,
                                                             const float *__restrict__ g2d, float *__restrict__ maxr,
@@ -1305,13 +1294,13 @@ __global__ __launch_bounds__(256) void activate_bwd_kernel(int64_t P, const floa
 // train_single.py:217-223), the sparse Adam's "any relevant row" flag (zeroed earlier in the step)
 // and the densification statistics of the same row (densify_stats_kernel's arithmetic).
 __global__ __launch_bounds__(256) void activate_bwd_step_kernel(
-    int64_t P, const float4 *__restrict__ q_raw, const float *__restrict__ scales, const float *__restrict__ opac,
-    const float *__restrict__ g_s, const float4 *__restrict__ g_q, const float *__restrict__ g_o,
-    float *__restrict__ d_s, float4 *__restrict__ d_q, float *__restrict__ d_o, int64_t skybox, int *__restrict__ flag,
-    const int *__restrict__ radii, const float *__restrict__ g2d, float *__restrict__ maxr, float *__restrict__ accum,
-    float *__restrict__ denom, int sparse_rows, const float *__restrict__ s_raw, const float *__restrict__ o_raw) {
-    // scales / opac NULL: the raw mode (the rasterizer read the pre-activation parameters): the
-    // activations are recomputed here from s_raw / o_raw, with the forward's expressions
+    int64_t P, const float4 *__restrict__ q_raw, const float *__restrict__ g_s, const float4 *__restrict__ g_q,
+    const float *__restrict__ g_o, float *__restrict__ d_s, float4 *__restrict__ d_q, float *__restrict__ d_o,
+    int64_t skybox, int *__restrict__ flag, const int *__restrict__ radii, const float *__restrict__ g2d,
+    float *__restrict__ maxr, float *__restrict__ accum, float *__restrict__ denom, int sparse_rows,
+    const float *__restrict__ s_raw, const float *__restrict__ o_raw) {
+    // the rasterizer read the pre-activation parameters: the activations are recomputed here from
+    // s_raw / o_raw, with the forward's expressions
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     float go = 0.f;
     if (i < P) {
@@ -1329,8 +1318,7 @@ __global__ __launch_bounds__(256) void activate_bwd_step_kernel(
         }
         if (live) {
 #pragma unroll
-            for (int k = 0; k < 3; k++)
-                d_s[3 * i + k] = g_s[3 * i + k] * (scales ? scales[3 * i + k] : act_scale(s_raw[3 * i + k]));
+            for (int k = 0; k < 3; k++) d_s[3 * i + k] = g_s[3 * i + k] * act_scale(s_raw[3 * i + k]);
             const float4 x = q_raw[i], g = g_q[i];
             const float n = sqrtf(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w);
             const float d = fmaxf(n, 1e-12f);
@@ -1339,7 +1327,7 @@ __global__ __launch_bounds__(256) void activate_bwd_step_kernel(
             const float gn = n >= 1e-12f && n != 0.f ? gd / n : 0.f;
             d_q[i] = make_float4(g.x / d + x.x * gn, g.y / d + x.y * gn, g.z / d + x.z * gn, g.w / d + x.w * gn);
         }
-        const float y = opac ? opac[i] : act_opacity(o_raw[i]);
+        const float y = act_opacity(o_raw[i]);
         go = i < skybox ? 0.f : g_o[i] * (1.f - y) * y;
         d_o[i] = go;
     }
@@ -1533,12 +1521,10 @@ dim3 stream_grid(int C, int H, int W) {
     return dim3((W + kStW - 1) / kStW, (H + seg - 1) / seg, C);
 }
 
-// GSR_SSIM_TILED=1 selects the 64 x 16 tile gradient kernel instead of the streaming one (same
-// bits; kept for the A/B test and measurements).  Read per call so a test can switch it.
-bool ssim_tiled() {
-    const char *e = std::getenv("GSR_SSIM_TILED");
-    return e != nullptr && e[0] == '1';
-}
+// gsr_set_ssim_kernel: 0 = the streaming gradient kernel, 1 = the 64 x 16 tile kernel (same bits;
+// the cross-check implementation the tests compare the streaming kernel against)
+std::atomic<int> g_ssim_kernel{0};
+bool ssim_tiled() { return g_ssim_kernel.load(std::memory_order_relaxed) == 1; }
 
 
 // ---- masked inverse-depth L1 (train_single.py:135-141) ----------------------------------------
@@ -1805,7 +1791,8 @@ void set_lds_attr() {
 int sparse_adam(int n_groups, const gsr_adam_group *groups, int64_t P, const float *relevance, double beta1,
                 double beta2, double eps, int *flag_scratch, bool flag_ready, hipStream_t s, float *shrink_raw,
                 int64_t shrink_first, float shrink_limit, const float *live3, int64_t skybox, int *row_list) {
-    if ((shrink_raw || live3) && adam_elementwise()) {
+    const int kernel = g_adam_kernel.load(std::memory_order_relaxed);  // read once: one choice per call
+    if ((shrink_raw || live3) && kernel == kAdamElementwise) {
         set_last_error("sparse Adam: the fused scale shrink / sparse rows need the row-block kernel");
         return GSR_ERR_UNSUPPORTED;
     }
@@ -1843,7 +1830,7 @@ int sparse_adam(int n_groups, const gsr_adam_group *groups, int64_t P, const flo
                            flag_scratch);
     }
     // torch applies python-float hyper-parameters as fp32 scalars: b, (1 - b) rounded from double
-    if (!relevance && !live3 && skybox == 0 && !shrink_raw && !adam_elementwise() && !adam_dense_rows()) {
+    if (!relevance && !live3 && skybox == 0 && !shrink_raw && kernel == kAdamAuto) {
         // the dense step: flat runs, and the row-block kernel for any group that is not one
         FlatAdamArgs fa;
         int rest[kMaxGroups], n_rest = 0;
@@ -1863,7 +1850,7 @@ int sparse_adam(int n_groups, const gsr_adam_group *groups, int64_t P, const flo
                                ShrinkArgs{nullptr, 0, 0.f}, DenseRows{nullptr, 0}, -1);
         }
     }
-    else if (!adam_elementwise())
+    else if (kernel != kAdamElementwise)
     {
         // the shrink reads the scales after their Adam update: it runs in the scaling group's wave
         int sh_group = -1;
@@ -1874,7 +1861,8 @@ int sparse_adam(int n_groups, const gsr_adam_group *groups, int64_t P, const flo
         AdamLaneMap lm;
         std::memset(&lm, 0, sizeof(lm));
         lm.sh_lane0 = -1;
-        bool fits = relevance != nullptr && !adam_rowblock() && (!shrink_raw || (sh_group >= 0 && groups[sh_group].width == 3));
+        bool fits = relevance != nullptr && kernel == kAdamAuto &&
+                    (!shrink_raw || (sh_group >= 0 && groups[sh_group].width == 3));
         for (int i = 0; fits && i < n_groups; i++) {
             if (lm.lanes + groups[i].width > kAdamListMaxLanes) {
                 fits = false;
@@ -2022,13 +2010,13 @@ int step_loss_backward(const float *img, const float *gt, const float *gmap, con
     return GSR_OK;
 }
 
-int step_activate_backward(int64_t P, const float *rotation_raw, const float *scales, const float *opac,
-                           const float *d_scales, const float *d_rots, const float *d_opac, float *scaling_grad,
-                           float *rotation_grad, float *opacity_grad, int64_t skybox, int *flag, const int *radii,
-                           const float *d_means2D, float *max_radii2D, float *accum, float *denom, hipStream_t s,
-                           bool sparse_rows, const float *scaling_raw, const float *opacity_raw) {
+int step_activate_backward(int64_t P, const float *rotation_raw, const float *d_scales, const float *d_rots,
+                           const float *d_opac, float *scaling_grad, float *rotation_grad, float *opacity_grad,
+                           int64_t skybox, int *flag, const int *radii, const float *d_means2D, float *max_radii2D,
+                           float *accum, float *denom, hipStream_t s, bool sparse_rows, const float *scaling_raw,
+                           const float *opacity_raw) {
     hipLaunchKernelGGL(activate_bwd_step_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P,
-                       reinterpret_cast<const float4 *>(rotation_raw), scales, opac, d_scales,
+                       reinterpret_cast<const float4 *>(rotation_raw), d_scales,
                        reinterpret_cast<const float4 *>(d_rots), d_opac, scaling_grad,
                        reinterpret_cast<float4 *>(rotation_grad), opacity_grad, skybox, flag, radii, d_means2D,
                        max_radii2D, accum, denom, sparse_rows ? 1 : 0, scaling_raw, opacity_raw);
@@ -2045,6 +2033,22 @@ int step_activate_backward(int64_t P, const float *rotation_raw, const float *sc
 using namespace gsr;
 
 extern "C" {
+
+int gsr_set_ssim_kernel(int kernel) {
+    if (kernel < 0 || kernel > 1) {
+        set_last_error("gsr_set_ssim_kernel: kernel 0 (streaming) or 1 (tiles)");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    return g_ssim_kernel.exchange(kernel);
+}
+
+int gsr_set_adam_kernel(int kernel) {
+    if (kernel < kAdamAuto || kernel > kAdamElementwise) {
+        set_last_error("gsr_set_adam_kernel: kernel 0 (default choice), 1 (row blocks) or 2 (element per thread)");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    return g_adam_kernel.exchange(kernel);
+}
 
 size_t gsr_l1_ssim_scratch_bytes(int C, int H, int W) {
     if (C <= 0 || H <= 0 || W <= 0) return 0;

@@ -36,7 +36,7 @@ namespace {
 enum Slot {
     kGeom, kBinning, kImage, kBwdScratch,                                  // rasterizer buffers
     kColor, kInvDepth, kExposed, kGradMap, kDColor, kDInvDepth,            // image-sized
-    kScales, kRots, kOpac, kDScales, kDRots, kDOpac, kDMeans2D, kRadii,    // per-Gaussian
+    kDScales, kDRots, kDOpac, kDMeans2D, kRadii,                           // per-Gaussian
     kLossScratch, kExpScratch, kDepthScratch, kWords,                      // small
     kAdamList,                                                             // sparse Adam's row list
     kSlots
@@ -59,14 +59,10 @@ struct gsr_train_ctx {
     int64_t growths = 0;  // gsr_train_ctx_stats
     // Stream-ordered growth (hipFreeAsync / hipMallocFromPoolAsync from the context's own memory pool,
     // which keeps what is freed): a training loop whose P and K grow over its densification events
-    // re-sizes its buffers without a host wait -- the synchronous form (GSR_STEP_SYNC_ALLOC=1: wait for
-    // the stream, hipFree, hipMalloc) stalls the host at every growth and hipMalloc of a large block
-    // maps its pages.  The pool is the context's, not the device's default pool, so other
-    // stream-ordered users in the process keep the default pool's release behaviour.
-    const bool async_alloc = [] {
-        const char *e = std::getenv("GSR_STEP_SYNC_ALLOC");
-        return !(e && e[0] == '1');
-    }();
+    // re-sizes its buffers without a host wait (waiting for the stream, hipFree and hipMalloc would
+    // stall the host at every growth, and hipMalloc of a large block maps its pages).  The pool is the
+    // context's, not the device's default pool, so other stream-ordered users in the process keep the
+    // default pool's release behaviour.
     bool pool_ready = false;
     hipMemPool_t pool = nullptr;
 
@@ -96,30 +92,15 @@ struct gsr_train_ctx {
         if (bytes <= b.cap && b.p) return b.p;
         growths++;
         const size_t want = std::max<size_t>(256, bytes + bytes / 4);
-        if (async_alloc) {
-            pool_setup();
-            // in stream order: work queued before (and the side streams joined into it) still reads the
-            // old block; everything after uses the new one
-            if (b.p) (void)hipFreeAsync(b.p, stream);
-            b.p = nullptr;
-            b.cap = 0;
-            const hipError_t e = pool ? hipMallocFromPoolAsync(&b.p, want, pool, stream)
-                                      : hipMallocAsync(&b.p, want, stream);
-            if (e != hipSuccess) {
-                b.p = nullptr;
-                failed_alloc = true;
-                return nullptr;
-            }
-            b.cap = want;
-            return b.p;
-        }
-        if (b.p) {  // queued kernels may still use the old allocation
-            if (hipStreamSynchronize(stream) != hipSuccess) return nullptr;
-            (void)hipFree(b.p);
-            b.p = nullptr;
-            b.cap = 0;
-        }
-        if (hipMalloc(&b.p, want) != hipSuccess) {
+        pool_setup();
+        // in stream order: work queued before (and the side streams joined into it) still reads the
+        // old block; everything after uses the new one
+        if (b.p) (void)hipFreeAsync(b.p, stream);
+        b.p = nullptr;
+        b.cap = 0;
+        const hipError_t e = pool ? hipMallocFromPoolAsync(&b.p, want, pool, stream)
+                                  : hipMallocAsync(&b.p, want, stream);
+        if (e != hipSuccess) {
             b.p = nullptr;
             failed_alloc = true;
             return nullptr;
@@ -135,15 +116,10 @@ struct gsr_train_ctx {
     float *f32(int slot, size_t n) { return static_cast<float *>(get(slot, n * sizeof(float))); }
 
     ~gsr_train_ctx() {
-        if (async_alloc) {
-            for (auto &b : buf)
-                if (b.p) (void)hipFreeAsync(b.p, stream);
-            (void)hipStreamSynchronize(stream);
-            if (pool) (void)hipMemPoolDestroy(pool);
-        } else {
-            for (auto &b : buf)
-                if (b.p) (void)hipFree(b.p);
-        }
+        for (auto &b : buf)
+            if (b.p) (void)hipFreeAsync(b.p, stream);
+        (void)hipStreamSynchronize(stream);
+        if (pool) (void)hipMemPoolDestroy(pool);
     }
 };
 
@@ -161,25 +137,14 @@ int fail_step(int rc, const char *what) {
     return rc;
 }
 
-// GSR_STEP_ACTIVATIONS=1: activations written by their own launch and read by the rasterizer (the
-// Python-driven step's form); default: the rasterizer and the activation backward read the raw
-// parameters and activate them where they are used (GaussianInputs.raw)
+// The rasterizer and the activation backward read the raw parameters and activate them where they
+// are used (GaussianInputs.raw); the Python-driven step writes the activations in a launch of their own.
 #ifndef GSR_STEP_FUSE_ACT
 #define GSR_STEP_FUSE_ACT 1
 #endif
 #ifndef GSR_STEP_PHOTO_IN_SSIM
 #define GSR_STEP_PHOTO_IN_SSIM 1  // 0: the SSIM pass writes G and the exposure backward forms the gradient
 #endif
-
-bool step_raw_params() {
-    const char *e = std::getenv("GSR_STEP_ACTIVATIONS");
-    return !(e != nullptr && e[0] == '1');
-}
-
-bool step_sparse_rows() {
-    const char *e = std::getenv("GSR_STEP_DENSE_ROWS");  // read per call: A/B runs switch it
-    return !(e != nullptr && e[0] == '1');
-}
 
 int invalid(const char *msg) {
     set_last_error(std::string("gsr_train_step: ") + msg);
@@ -194,7 +159,7 @@ gsr_train_ctx *gsr_train_ctx_create(void) { return new (std::nothrow) gsr_train_
 
 int gsr_train_ctx_stats(const gsr_train_ctx *ctx, int64_t *out, int n) {
     if (!ctx || !out || n < 0) return invalid("NULL context or stats buffer");
-    const int64_t v[3] = {ctx->growths, ctx->held(), ctx->async_alloc ? 1 : 0};
+    const int64_t v[3] = {ctx->growths, ctx->held(), 1};  // [2]: the buffers grow in stream order
     int k = 0;
     for (; k < n && k < 3; k++) out[k] = v[k];
     return k;
@@ -244,7 +209,6 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
     const int64_t npix = (int64_t)W * H;
     const bool depth = a->mono_invdepth != nullptr && a->depth_weight > 0.f;
 
-    float *scales = ctx->f32(kScales, 3 * P), *rots = ctx->f32(kRots, 4 * P), *opac = ctx->f32(kOpac, P);
     float *d_scales = ctx->f32(kDScales, 3 * P), *d_rots = ctx->f32(kDRots, 4 * P), *d_opac = ctx->f32(kDOpac, P);
     float *d_means2D = ctx->f32(kDMeans2D, 3 * P);
     int *radii = static_cast<int *>(ctx->get(kRadii, sizeof(int) * P));
@@ -260,7 +224,7 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
     void *words = ctx->get(kWords, 64);
     // the sparse Adam's compacted row list (grow-only; without it the row-block kernel runs)
     int *adam_list = static_cast<int *>(ctx->get(kAdamList, sizeof(int) * ((size_t)P + 64)));
-    if (ctx->failed_alloc || !scales || !rots || !opac || !d_scales || !d_rots || !d_opac || !d_means2D || !radii ||
+    if (ctx->failed_alloc || !d_scales || !d_rots || !d_opac || !d_means2D || !radii ||
         !color || !invd || !image || !gmap || !d_color || !d_invd || !loss_scratch || !exp_scratch ||
         !depth_scratch || !words) {
         ctx->failed_alloc = false;
@@ -277,17 +241,12 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
     }
     int rc;
 
-    // render(): activations, rasterizer, exposure of this view (harness.py TrainStep.render).  Raw
-    // mode: the preprocess activates the parameters it reads (no activated copy written and re-read)
-    const bool raw = step_raw_params();
-    if (!raw && (rc = gsr_activate_forward(P, a->scaling, a->rotation, a->opacity, scales, rots, opac, sv)))
-        return fail_step(rc, "activations");
-    const float *r_scales = raw ? a->scaling : scales, *r_rots = raw ? a->rotation : rots,
-                *r_opac = raw ? a->opacity : opac;
+    // render(): activations, rasterizer, exposure of this view (harness.py TrainStep.render).  The
+    // preprocess activates the raw parameters it reads (no activated copy written and re-read)
     int64_t K = 0;
-    set_raw_params(raw);
+    set_raw_params(true);
     rc = gsr_rasterize_forward_ex(resize_geom, resize_binning, resize_image, ctx, (int)P, a->D, a->M, a->background,
-                                  W, H, a->xyz, a->features, nullptr, r_opac, r_scales, 1.0f, r_rots, nullptr,
+                                  W, H, a->xyz, a->features, nullptr, a->opacity, a->scaling, 1.0f, a->rotation, nullptr,
                                   a->viewmatrix, a->projmatrix, a->campos, a->tan_fovx, a->tan_fovy, 0, color, invd,
                                   radii, nullptr, nullptr, nullptr, nullptr, 0, 0, sv, &K, 0);
     set_raw_params(false);
@@ -328,28 +287,27 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
     }
     // sparse gradient rows (gsr_launch.h GaussianGrads): the Gaussians no pixel's backward reached
     // (88% of the bench scene) have zero gradients and are never relevant to the sparse Adam, so
-    // their 232 B of gradient rows are not written (GSR_STEP_DENSE_ROWS=1: every row, as the
-    // Python-driven step)
-    const bool sparse_rows = step_sparse_rows();
+    // their 232 B of gradient rows are not written (dense_rows: every row, as the Python-driven step)
+    const bool sparse_rows = a->dense_rows == 0;
     // the activation backward (skybox lock, relevance flag, densification statistics:
     // train_single.py:193-194, 217-223) fused into the rasterizer backward's live-row pass, which
     // then writes the raw parameters' gradients itself (gsr_launch.h StepAct); the conditions
     // mirror backward.hip's split path (GSR_STEP_FUSE_ACT=0: the separate activation backward)
-    const bool fuse_act = GSR_STEP_FUSE_ACT && raw && sparse_rows && a->M == 16 &&
+    const bool fuse_act = GSR_STEP_FUSE_ACT && sparse_rows && a->M == 16 &&
                           (reinterpret_cast<uintptr_t>(a->features) & 15u) == 0 &&
                           (reinterpret_cast<uintptr_t>(a->features_grad) & 15u) == 0;
     const StepAct act{a->scaling, a->opacity, reinterpret_cast<const float4 *>(a->rotation), a->skybox_rows, radii,
                       a->max_radii2D, a->xyz_gradient_accum, a->denom, flag, 1};
     set_sparse_grad_rows(sparse_rows);
-    set_raw_params(raw);
+    set_raw_params(true);
     set_step_act(fuse_act ? &act : nullptr);
     rc = gsr_rasterize_backward(resize_scratch, ctx, (int)P, a->D, a->M, K, a->background, W, H, a->xyz,
-                                     a->features, nullptr, r_scales, 1.0f, r_rots, nullptr, a->viewmatrix, a->projmatrix,
-                                     a->campos, a->tan_fovx, a->tan_fovy, radii, buf_ptr(ctx, kGeom),
-                                     buf_ptr(ctx, kBinning), buf_ptr(ctx, kImage), d_color, depth ? d_invd : nullptr,
-                                     d_means2D, nullptr, fuse_act ? a->opacity_grad : d_opac, a->xyz_grad, nullptr,
-                                     a->features_grad, fuse_act ? a->scaling_grad : d_scales,
-                                     fuse_act ? a->rotation_grad : d_rots, nullptr, nullptr, nullptr, nullptr, 0, 0, sv);
+                                a->features, nullptr, a->scaling, 1.0f, a->rotation, nullptr, a->viewmatrix,
+                                a->projmatrix, a->campos, a->tan_fovx, a->tan_fovy, radii, buf_ptr(ctx, kGeom),
+                                buf_ptr(ctx, kBinning), buf_ptr(ctx, kImage), d_color, depth ? d_invd : nullptr,
+                                d_means2D, nullptr, fuse_act ? a->opacity_grad : d_opac, a->xyz_grad, nullptr,
+                                a->features_grad, fuse_act ? a->scaling_grad : d_scales,
+                                fuse_act ? a->rotation_grad : d_rots, nullptr, nullptr, nullptr, nullptr, 0, 0, sv);
     set_sparse_grad_rows(false);
     set_raw_params(false);
     set_step_act(nullptr);
@@ -358,10 +316,9 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
         return invalid("the rasterizer backward did not take the fused activation backward it was given");
     // otherwise the activation backward on its own; then the sparse Adam and the shrink (:225-241)
     if (!fuse_act &&
-        (rc = step_activate_backward(P, a->rotation, raw ? nullptr : scales, raw ? nullptr : opac, d_scales, d_rots,
-                                     d_opac, a->scaling_grad, a->rotation_grad, a->opacity_grad, a->skybox_rows, flag,
-                                     radii, d_means2D, a->max_radii2D, a->xyz_gradient_accum, a->denom, s, sparse_rows,
-                                     a->scaling, a->opacity)))
+        (rc = step_activate_backward(P, a->rotation, d_scales, d_rots, d_opac, a->scaling_grad, a->rotation_grad,
+                                     a->opacity_grad, a->skybox_rows, flag, radii, d_means2D, a->max_radii2D,
+                                     a->xyz_gradient_accum, a->denom, s, sparse_rows, a->scaling, a->opacity)))
         return fail_step(rc, "activation backward");
     if (!a->skip_gaussian_step &&
         (rc = sparse_adam(a->n_groups, a->groups, P, a->opacity_grad, a->beta1, a->beta2, a->eps, flag, true, s,

@@ -124,6 +124,13 @@ def set_fwd_split_min(length: int) -> int:
     return r
 
 
+def set_fwd_early_workers(enable: bool) -> bool:
+    """gsr_set_fwd_early_workers: True (default) launches the forward split's worker pool ahead of
+    tile_order on a side stream, False beside render_fwd.  Same images either way.  Process-wide;
+    returns the previous setting."""
+    return bool(_L.gsr_set_fwd_early_workers(int(bool(enable))))
+
+
 def set_live_list(enable: bool) -> bool:
     """gsr_set_live_list: True walks the backward's live rows through one list spread over the chip
     (rows in spatial order: gs_train.chunk.reorder_rows); False (default) per 2048-row range.  Same

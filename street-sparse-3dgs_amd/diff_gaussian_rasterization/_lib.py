@@ -45,7 +45,7 @@ class TrainStepArgs(ctypes.Structure):
                 ("exposure_beta1", ctypes.c_double), ("exposure_beta2", ctypes.c_double),
                 ("exposure_eps", ctypes.c_double), ("skybox_rows", _i64), ("scaffold_rows", _i64),
                 ("max_scale", _f), ("losses", _vp), ("stream", _vp), ("depth_only", _i),
-                ("depth_dens_weight", ctypes.c_double), ("skip_gaussian_step", _i)]
+                ("depth_dens_weight", ctypes.c_double), ("skip_gaussian_step", _i), ("dense_rows", _i)]
 
 
 # exported symbol -> (restype, argtypes); must match include/gsr.h, gsr_train.h, gsr_hier.h, gsr_knn.h, gsr_densify.h
@@ -71,6 +71,7 @@ SIGNATURES = {
     "gsr_set_split_gate": (_i, [_i]),
     "gsr_set_live_list": (_i, [_i]),
     "gsr_set_fwd_split_min": (_i, [_i]),
+    "gsr_set_fwd_early_workers": (_i, [_i]),
     "gsr_set_fwd_spin_limits": (_i, [_i64, _i64]),
     "gsr_segment_layout_check": (_i, [ctypes.c_int64, _i, _i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "gsr_frame_stats": (_i, [_vp, _i, _i, _i, ctypes.POINTER(_i64), _i]),
@@ -92,6 +93,8 @@ SIGNATURES = {
     "gsr_l1_ssim_backward_from_map": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "gsr_photo_loss_forward": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp]),
     "gsr_photo_loss_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp]),
+    "gsr_set_ssim_kernel": (_i, [_i]),
+    "gsr_set_adam_kernel": (_i, [_i]),
     "gsr_sparse_adam_step": (_i, [_i, ctypes.POINTER(AdamGroup), _i64, _vp, ctypes.c_double, ctypes.c_double,
                                   ctypes.c_double, _vp, _vp]),
     "gsr_densify_stats": (_i, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -144,7 +147,7 @@ GT_SIGNATURES = {
     "gsr_densify_plan_gt": (_i, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _d, _vp, _vp, _vp]),
 }
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 _lib = None
 
 

@@ -14,7 +14,7 @@ objects'.  The gradients land in persistent buffers (`grads`) instead of `.grad`
 as after TrainStep's zero_grad(set_to_none=True).  `grads` is sparse by default: the opacity
 gradient is written for every row each step, the other rows only for the Gaussians the backward
 reached this step (every other row's gradient is zero by definition and its buffer row keeps an
-older value; the buffers start zeroed).  GSR_STEP_DENSE_ROWS=1 writes every row.
+older value; the buffers start zeroed).  `dense_rows = True` on the step writes every row.
 """
 from __future__ import annotations
 
@@ -32,6 +32,8 @@ _PARAMS = ("_xyz", "_features", "_opacity", "_scaling", "_rotation")
 
 
 class NativeTrainStep(TrainStep):
+    dense_rows = False  # True: every gradient row is written each step (gsr_train_step_args.dense_rows)
+
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
         self._ctx = None
@@ -198,6 +200,7 @@ class NativeTrainStep(TrainStep):
         a.depth_only = int(depth_only)
         a.depth_dens_weight = self.dens_weight
         a.skip_gaussian_step = int(between is not None)
+        a.dense_rows = int(bool(self.dense_rows))
         losses = torch.empty(6, dtype=torch.float32, device=dev)  # a fresh tensor per step, as TrainStep's
         a.losses = losses.data_ptr()
         a.stream = stream(dev).value

@@ -44,6 +44,48 @@ def test_library_metadata_calls_without_gpu():
     assert L.gsr_stage_times_ms(buf, 8) >= 0
 
 
+# setter -> (documented default, the other valid values, out-of-range values)
+KERNEL_SETTERS = {"gsr_set_fwd_early_workers": (1, (0,), (-1, 2)),
+                  "gsr_set_ssim_kernel": (0, (1,), (-1, 2)),
+                  "gsr_set_adam_kernel": (0, (1, 2), (-1, 3))}
+
+
+@pytest.mark.parametrize("name", sorted(KERNEL_SETTERS))
+def test_kernel_setters_return_previous_and_reject_bad_values(name):
+    """The explicit settings that replaced the library's environment switches (host state only, no
+    GPU): the first call returns the documented default, the next one the value just set, an
+    out-of-range value fails with GSR_ERR_INVALID_ARGUMENT and leaves the setting as it was."""
+    from diff_gaussian_rasterization import _lib
+    GSR_ERR_INVALID_ARGUMENT = -1
+    setter = getattr(_lib.load(), name)
+    default, others, bad = KERNEL_SETTERS[name]
+    try:
+        assert setter(default) == default
+        prev = default
+        for v in others + (default,):
+            assert setter(v) == prev
+            prev = v
+            for b in bad:
+                assert setter(b) == GSR_ERR_INVALID_ARGUMENT
+                assert name.encode() in _lib.load().gsr_last_error()
+                assert setter(v) == v  # unchanged by the rejected call
+    finally:
+        setter(default)
+
+
+def test_native_sources_read_no_environment():
+    """libgsr_hip.so's behaviour is set through its C ABI (gsr_set_*, per-call arguments) or at
+    build time (-D variants), never through the caller's environment."""
+    pkg = os.path.join(REPO, "street-sparse-3dgs_amd")
+    n = 0
+    for sub in ("csrc", "host"):
+        for root, _, files in os.walk(os.path.join(pkg, sub)):
+            for f in files:
+                n += 1
+                assert "getenv" not in open(os.path.join(root, f), errors="replace").read(), f
+    assert n >= 15  # the sources were found
+
+
 # (L, Lf) -> the largest extension of the binning buffer past the point and level-1 lists' own room,
 # as a fraction of that room, at K >= 1M (the default 512 / 2048 measured 5.2%; 512 / 1024 40%)
 SEG_EXTENSION_BOUND = {(512, 0): 0.0, (0, 4096): 0.0, (512, 4096): 0.0, (512, 2048): 0.08, (512, 1024): 0.45,

@@ -422,14 +422,13 @@ def test_native_step_after_optimizer_load_state_dict():
     _assert_equal_snapshots(out[False], out[True])
 
 
-def test_native_dense_fallback_zeroes_skybox_rows(monkeypatch):
-    """GSR_STEP_DENSE_ROWS=1 and only the locked skybox rows blending: their opacity gradient is
+def test_native_dense_fallback_zeroes_skybox_rows():
+    """NativeTrainStep.dense_rows and only the locked skybox rows blending: their opacity gradient is
     locked at zero, no row is relevant and OurAdam's dense fallback updates every row -- with all six
     of the skybox rows' gradients zero (train_single.py:217-223), as the Python step has them."""
     from helpers import deterministic
     from gs_train.harness import make_problem
     from gs_train.native_step import NativeTrainStep
-    monkeypatch.setenv("GSR_STEP_DENSE_ROWS", "1")
     S = 2000
     out = {}
     with deterministic():
@@ -437,6 +436,8 @@ def test_native_dense_fallback_zeroes_skybox_rows(monkeypatch):
             torch.manual_seed(0)
             ts = make_problem(20_000, 256, 192, n_views=2, seed=4, step_cls=NativeTrainStep if native else None,
                               depth=True, skybox_points=S)
+            if native:
+                ts.dense_rows = True
             torch.manual_seed(3)
             ts.step()
             with torch.no_grad():

@@ -79,6 +79,16 @@ def fwd_segment(L):
         _C.set_fwd_segment(prev)
 
 
+@contextlib.contextmanager
+def fwd_early_workers(enable):
+    from diff_gaussian_rasterization import _C
+    prev = _C.set_fwd_early_workers(enable)
+    try:
+        yield
+    finally:
+        _C.set_fwd_early_workers(prev)
+
+
 def max_tile_work(h, c):
     nc = h["state"]["n_contrib"].reshape(c["H"], c["W"])
     gy, gx = (c["H"] + 15) // 16, (c["W"] + 15) // 16
@@ -253,23 +263,22 @@ def test_fwd_segments_deterministic_and_repeatable():
 
 
 @pytest.mark.parametrize("c", [FWD_CASES[0], FWD_CASES[2]], ids=[FWD_CASES[0]["name"], FWD_CASES[2]["name"]])
-def test_fwd_workers_launched_ahead_equal_beside(c, monkeypatch):
-    """GSR_FWD_EARLY_WORKERS=1 launches the worker pool before tile_order (waiting for its queue
+def test_fwd_workers_launched_ahead_equal_beside(c):
+    """gsr_set_fwd_early_workers(1) launches the worker pool before tile_order (waiting for its queue
     release); the items, their order of sums and so the frame are those of the pool launched beside
     render_fwd: record mode bitwise equal, and the oracle's bars."""
     s = seg_scene(c)
     dcol, dinv = upstream_grads(c)
     st, g = run_oracle(s, c, dcol, dinv)
     out = {}
-    for e in ("1", "0", "1"):
-        monkeypatch.setenv("GSR_FWD_EARLY_WORKERS", e)
-        with deterministic(), fwd_segment(4096), bwd_segment(512):
+    for e in (1, 0, 1):
+        with fwd_early_workers(e), deterministic(), fwd_segment(4096), bwd_segment(512):
             out.setdefault(e, []).append(run_hip(s, c, dcol, dinv))
-    fwd_compare(c, st, g, out["1"][0])
-    for h in (out["0"][0], out["1"][1]):
-        np.testing.assert_array_equal(out["1"][0]["color"], h["color"])
-        np.testing.assert_array_equal(out["1"][0]["state"]["n_contrib"], h["state"]["n_contrib"])
-        for k, v in out["1"][0]["grads"].items():
+    fwd_compare(c, st, g, out[1][0])
+    for h in (out[0][0], out[1][1]):
+        np.testing.assert_array_equal(out[1][0]["color"], h["color"])
+        np.testing.assert_array_equal(out[1][0]["state"]["n_contrib"], h["state"]["n_contrib"])
+        for k, v in out[1][0]["grads"].items():
             if v is not None:
                 np.testing.assert_array_equal(v, h["grads"][k], err_msg=k)
 
@@ -390,18 +399,17 @@ def fwd_spin_limits(ready=0, flag=0):
         _C.set_fwd_spin_limits(0, 0)
 
 
-def test_fwd_workers_that_give_up_on_the_queue_leave_the_frame_exact(monkeypatch):
+def test_fwd_workers_that_give_up_on_the_queue_leave_the_frame_exact():
     """The early pool's workers wait for tile_order's release of the queue on another stream; if they
     give up (here: a ready-spin limit of one trip, as when the two streams do not run concurrently),
     they are counted (forward_stats) and the pool's second launch after render_fwd blends every item:
     record mode, the frame bitwise the normal one's.  ready = -1 makes every worker leave at once
     (normally tile_order has released the queue before the side stream's workers even start)."""
     from diff_gaussian_rasterization import _C
-    monkeypatch.setenv("GSR_FWD_EARLY_WORKERS", "1")
     c = FWD_CASES[0]
     s = seg_scene(c)
     dcol, dinv = upstream_grads(c)
-    with deterministic(), fwd_segment(4096), bwd_segment(512):
+    with fwd_early_workers(1), deterministic(), fwd_segment(4096), bwd_segment(512):
         ref = run_hip(s, c, dcol, dinv)
         g0 = _C.forward_stats()["fwd_worker_giveups"]
         with fwd_spin_limits(ready=-1):

@@ -10,6 +10,7 @@ Tolerances (fp32 kernels vs fp32/fp64 references):
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import numpy as np
@@ -99,9 +100,9 @@ def test_l1_ssim_map_path_equals_direct_backward(shape):
 
 
 @pytest.mark.parametrize("shape", [(3, 1080, 1920), (3, 77, 131), (1, 200, 64), (2, 64, 63), (1, 5, 9)])
-def test_l1_ssim_streaming_equals_tiled(shape, monkeypatch):
+def test_l1_ssim_streaming_equals_tiled(shape):
     """The streaming gradient kernel (64 x 64 strips, LDS rings) and the 64 x 16 tile kernel form
-    every value with the same fmaf order: G and dx must agree bit for bit (GSR_SSIM_TILED=1
+    every value with the same fmaf order: G and dx must agree bit for bit (gsr_set_ssim_kernel(1)
     selects the tile kernel)."""
     from gs_train._native import lib, ptr, stream
     g = torch.Generator().manual_seed(11)
@@ -112,19 +113,35 @@ def test_l1_ssim_streaming_equals_tiled(shape, monkeypatch):
     L = lib()
     scratch = torch.empty(L.gsr_l1_ssim_scratch_bytes(C, H, W), dtype=torch.uint8, device=DEV)
     res = {}
-    for tiled in ("0", "1"):
-        monkeypatch.setenv("GSR_SSIM_TILED", tiled)
-        dx = torch.empty_like(img)
-        gmap = torch.empty_like(img)
-        out = torch.empty(2, device=DEV)
-        s = stream(img.device)
-        assert L.gsr_l1_ssim_backward(ptr(img), ptr(gt), C, H, W, ptr(up), ptr(dx), s) == 0
-        assert L.gsr_l1_ssim_forward_with_map(ptr(img), ptr(gt), C, H, W, ptr(scratch), ptr(out), ptr(gmap), s) == 0
-        torch.cuda.synchronize()
-        res[tiled] = (dx, gmap, out)
-    assert torch.equal(res["0"][0], res["1"][0])
-    assert torch.equal(res["0"][1], res["1"][1])
-    assert torch.allclose(res["0"][2], res["1"][2], rtol=0, atol=1e-6)
+    prev = L.gsr_set_ssim_kernel(0)
+    try:
+        for tiled in (0, 1):
+            assert L.gsr_set_ssim_kernel(tiled) >= 0
+            dx = torch.empty_like(img)
+            gmap = torch.empty_like(img)
+            out = torch.empty(2, device=DEV)
+            s = stream(img.device)
+            assert L.gsr_l1_ssim_backward(ptr(img), ptr(gt), C, H, W, ptr(up), ptr(dx), s) == 0
+            assert L.gsr_l1_ssim_forward_with_map(ptr(img), ptr(gt), C, H, W, ptr(scratch), ptr(out), ptr(gmap), s) == 0
+            torch.cuda.synchronize()
+            res[tiled] = (dx, gmap, out)
+    finally:
+        L.gsr_set_ssim_kernel(prev)
+    assert torch.equal(res[0][0], res[1][0])
+    assert torch.equal(res[0][1], res[1][1])
+    assert torch.allclose(res[0][2], res[1][2], rtol=0, atol=1e-6)
+
+
+@contextlib.contextmanager
+def adam_kernel(mode):
+    """gsr_set_adam_kernel: 0 the default choice, 1 row blocks for every step, 2 element per thread."""
+    from gs_train._native import lib
+    prev = lib().gsr_set_adam_kernel(mode)
+    assert prev >= 0, prev
+    try:
+        yield
+    finally:
+        lib().gsr_set_adam_kernel(prev)
 
 
 def _adam_from_fixture(use_index):
@@ -307,9 +324,9 @@ def test_native_step_equals_python_step(depth, alpha, skybox, scaffold):
 
 
 @pytest.mark.parametrize("dense_rows", ["0", "1"])
-def test_native_step_sparse_rows_and_dense_fallback(dense_rows, monkeypatch):
+def test_native_step_sparse_rows_and_dense_fallback(dense_rows):
     """The native step's sparse gradient rows (gradient rows of Gaussians no pixel's backward
-    reached are not written: GSR_STEP_DENSE_ROWS unset) and its dense rows give the Python-driven
+    reached are not written: NativeTrainStep.dense_rows False) and its dense rows give the Python-driven
     step's bits, including the sparse Adam's dense fallback: after two ordinary steps every opacity
     is pushed to ~0, no pixel blends, no row is relevant and OurAdam updates every row with zero
     gradients (train_single.py:226-231, OurAdam.py:214) -- the skybox rows' six gradients zeroed
@@ -317,7 +334,6 @@ def test_native_step_sparse_rows_and_dense_fallback(dense_rows, monkeypatch):
     from helpers import deterministic
     from gs_train.harness import make_problem
     from gs_train.native_step import NativeTrainStep
-    monkeypatch.setenv("GSR_STEP_DENSE_ROWS", dense_rows)
     names = ("_xyz", "_features", "_opacity", "_scaling", "_rotation")
     out = {}
     with deterministic():
@@ -325,6 +341,8 @@ def test_native_step_sparse_rows_and_dense_fallback(dense_rows, monkeypatch):
             torch.manual_seed(0)
             ts = make_problem(20_000, 256, 192, n_views=2, seed=4, step_cls=NativeTrainStep if native else None,
                               depth=True, skybox_points=300)
+            if native:
+                ts.dense_rows = dense_rows == "1"
             torch.manual_seed(3)
             ts.step()
             ts.step()
@@ -486,9 +504,10 @@ def test_adam_column_blocks_equal_separate_groups():
 
 
 @pytest.mark.parametrize("frac", [0.12, 0.9, 0.0, 1.0])
-def test_sparse_adam_row_blocks_equal_elementwise(frac, monkeypatch):
-    """The row-block Adam kernel (one wave per 64 rows) and the element-per-thread kernel apply
-    the same per-element arithmetic: parameters and moments bit-identical, for sparse and dense
+def test_sparse_adam_row_blocks_equal_elementwise(frac):
+    """The default choice (this 59-element row fits one wave: the compacted row-list kernel), the
+    row-block Adam kernel (one wave per 64 rows) and the element-per-thread kernel apply the same
+    per-element arithmetic (gsr_set_adam_kernel 0, 1, 2): parameters and moments bit-identical, for sparse and dense
     relevance (frac 0: no relevant row, the dense fallback; frac 1: every wave fully relevant, the
     joined (P,16,3) column blocks then updated as whole float4 rows) and joined column blocks."""
     from gs_train import Adam
@@ -500,27 +519,28 @@ def test_sparse_adam_row_blocks_equal_elementwise(frac, monkeypatch):
     for gr in grads:
         gr[2][torch.rand(P, generator=g) >= frac] = 0.0
     out = {}
-    for mode in ("0", "1"):
-        monkeypatch.setenv("GSR_ADAM_ELEMENTWISE", mode)
+    for mode in (0, 1, 2):
         params = [torch.nn.Parameter(h.to(DEV)) for h in init]
         groups = [{"params": [params[0]], "lr": 1.6e-4},
                   {"params": [params[1]], "lr": 2.5e-3, "column_lrs": [(0, 3, 2.5e-3), (3, 48, 1.25e-4)]},
                   {"params": [params[2]], "lr": 5e-2}, {"params": [params[3]], "lr": 5e-3},
                   {"params": [params[4]], "lr": 1e-3}]
         opt = Adam(groups, lr=0.0, eps=1e-15)
-        for gr in grads:
-            for p, x in zip(params, gr):
-                p.grad = x.to(DEV)
-            opt.step(relevance=params[2].grad)
-        torch.cuda.synchronize()
+        with adam_kernel(mode):
+            for gr in grads:
+                for p, x in zip(params, gr):
+                    p.grad = x.to(DEV)
+                opt.step(relevance=params[2].grad)
+            torch.cuda.synchronize()
         out[mode] = [t.detach().clone() for p in params
                      for t in (p, opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"])]
-    for a, b in zip(out["0"], out["1"]):
-        assert torch.equal(a, b)
+    for mode in (1, 2):
+        for a, b in zip(out[0], out[mode]):
+            assert torch.equal(a, b), mode
 
 
 @pytest.mark.parametrize("P", [70_001, 1])
-def test_dense_adam_flat_runs_equal_row_blocks(P, monkeypatch):
+def test_dense_adam_flat_runs_equal_row_blocks(P):
     """The dense step (no relevance: torch.optim.Adam over every element, train_post's optimizer)
     streams each group as one flat float4 run and merges a column-split pair into whole rows.
     Parameters and moments are bit-identical to the row-block and element-per-thread kernels, for
@@ -532,9 +552,7 @@ def test_dense_adam_flat_runs_equal_row_blocks(P, monkeypatch):
     init = [torch.randn((P,) + s, generator=g) for s in shapes]
     grads = [[torch.randn((P,) + s, generator=g) for s in shapes] for _ in range(3)]
     out = {}
-    for mode in ("flat", "rows", "elementwise"):
-        monkeypatch.setenv("GSR_ADAM_DENSE_ROWS", "1" if mode == "rows" else "0")
-        monkeypatch.setenv("GSR_ADAM_ELEMENTWISE", "1" if mode == "elementwise" else "0")
+    for mode, kernel in (("flat", 0), ("rows", 1), ("elementwise", 2)):
         params = [torch.nn.Parameter(h.to(DEV)) for h in init]
         # an (P, 4) parameter whose storage starts 4 B past a 16-B boundary: the scalar run
         store = torch.zeros(P * 4 + 1, device=DEV)
@@ -547,12 +565,13 @@ def test_dense_adam_flat_runs_equal_row_blocks(P, monkeypatch):
                   {"params": [params[4]], "lr": 7e-3, "column_lrs": [(0, 2, 7e-3), (2, 6, 3e-3)]},
                   {"params": [odd], "lr": 4e-3}]
         opt = Adam(groups, lr=0.0, eps=1e-15)
-        for gr in grads:
-            for p, x in zip(params[:5], gr[:5]):
-                p.grad = x.to(DEV)
-            odd.grad = gr[5][:, :4].contiguous().to(DEV)
-            opt.step()
-        torch.cuda.synchronize()
+        with adam_kernel(kernel):
+            for gr in grads:
+                for p, x in zip(params[:5], gr[:5]):
+                    p.grad = x.to(DEV)
+                odd.grad = gr[5][:, :4].contiguous().to(DEV)
+                opt.step()
+            torch.cuda.synchronize()
         out[mode] = [t.detach().clone() for p in params[:5] + [odd]
                      for t in (p, opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"])]
     for name in ("rows", "elementwise"):
