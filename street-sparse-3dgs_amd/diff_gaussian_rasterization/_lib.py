@@ -147,6 +147,15 @@ GT_SIGNATURES = {
     "gsr_densify_plan_gt": (_i, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _d, _vp, _vp, _vp]),
 }
 
+# include/gsr_eval.h (the evaluation metrics); typed by load() like SIGNATURES
+EVAL_SIGNATURES = {
+    "gsr_eval_depth_range_bits": (_i, [_vp, _i64, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _i, _vp, _vp]),
+    "gsr_eval_color_bits": (_i, [_vp, _i64, _i, ctypes.POINTER(ctypes.c_uint8), _i, _vp, _vp]),
+    "gsr_eval_frame_scratch_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "gsr_eval_frame": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "gsr_eval_accumulate": (_i, [_vp, _i, _vp, _vp]),
+}
+
 ABI_VERSION = 7
 _lib = None
 
@@ -168,7 +177,7 @@ def load(path: str = LIB_PATH):
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the host
         raise RasterizerLibraryError(f"failed to load {path}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GT_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

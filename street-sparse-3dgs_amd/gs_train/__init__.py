@@ -10,6 +10,7 @@
   harness.TrainStep                one train_single.py inner-loop iteration (the "train-step ms")
   native_step.NativeTrainStep      the same iteration as one native call (gsr_train_step)
   synthetic                        seeded synthetic scenes / cameras
+  evaluate.Evaluator               test-set PSNR / SSIM / iMAE / iRMSE, whole-image and per region (csrc/eval.hip)
 """
 from .loss import l1_ssim, photo_loss  # noqa: F401
 from .optim import Adam  # noqa: F401
