@@ -156,6 +156,14 @@ EVAL_SIGNATURES = {
     "gsr_eval_accumulate": (_i, [_vp, _i, _vp, _vp]),
 }
 
+# include/gsr_hier_build.h (the LOD hierarchy builder); typed by load() like SIGNATURES
+HIER_BUILD_SIGNATURES = {
+    "gsr_hier_build_scratch_bytes": (ctypes.c_size_t, [_i64]),
+    "gsr_hier_build": (_i, [_i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                            ctypes.POINTER(_i), _vp, ctypes.c_size_t, _vp]),
+    "gsr_hier_build_stage_ms": (_i, [ctypes.POINTER(_f), _i]),
+}
+
 ABI_VERSION = 7
 _lib = None
 
@@ -177,7 +185,8 @@ def load(path: str = LIB_PATH):
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the host
         raise RasterizerLibraryError(f"failed to load {path}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GT_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(GT_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
+                              + list(HIER_BUILD_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -12,8 +12,10 @@ on the GPU, as the reference keeps them (scene/gaussian_model.py:424-425).  `vie
 and unused, as in the published cut (the reference passes zeros).  The outputs are written in
 place; expand_to_size returns the cut length (one host read, as upstream).
 
-The .hier file I/O of the extension (load_hierarchy / write_hierarchy) is not part of the
-rasterizer's hot path and its binary format is not vendored here: both raise.
+The .hier file I/O of the extension (load_hierarchy / write_hierarchy) reads and writes the
+uncompressed layout restated below (parity-unpinned: the format is not vendored in the reference);
+the half-precision "compressed" variant raises.  gs_train.hier_build produces the hierarchies
+write_hierarchy stores.
 """
 from __future__ import annotations
 

@@ -11,6 +11,7 @@
   native_step.NativeTrainStep      the same iteration as one native call (gsr_train_step)
   synthetic                        seeded synthetic scenes / cameras
   evaluate.Evaluator               test-set PSNR / SSIM / iMAE / iRMSE, whole-image and per region (csrc/eval.hip)
+  hier_build.build_hierarchy       a trained chunk's LOD hierarchy (GaussianHierarchyCreator's step; csrc/hier_build.hip)
 """
 from .loss import l1_ssim, photo_loss  # noqa: F401
 from .optim import Adam  # noqa: F401
