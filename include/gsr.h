@@ -226,8 +226,11 @@ int gsr_set_binning(int mode);
  * for tile_order's release of their queue (the side stream did not run beside the main one; the
  * pool's second launch completed those frames exactly -- ABI 5), out[5] = host nanoseconds spent waiting
  * for K (num_rendered) in forward calls, out[6] / out[7] = frames forwarded with the forward split /
- * the tile binning's superblock split armed (gsr_set_split_gate; ABI 5).  Returns the number of
- * values written (<= n). */
+ * the tile binning's superblock split armed (gsr_set_split_gate; ABI 5), out[8] = frames whose depth
+ * sort took its fourth pass (a visible depth outside the three-pass window, at or beyond 13107.2),
+ * out[9] = frames completed by a sort pass queued after K was read (0 in this build: every frame
+ * queues the four launches).  A caller that asks for 8 gets the first 8.  Returns the number of values
+ * written (<= n). */
 int gsr_forward_stats(int64_t *out, int n);
 
 /* The forward-split worker pool's time since load (or the last reset), in s_memrealtime ticks of

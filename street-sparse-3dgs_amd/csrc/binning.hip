@@ -19,16 +19,17 @@
 // laid out SB-major instead of row-major; every consumer goes through `ranges`, so the layout of
 // whole tiles in point_list is free.  Traffic ~ 8 B per SB instance + 4 B per tile instance written.
 //
-// Two ways to reach depth order (rasterizer.hip picks per frame):
-//   local sort (default)  level 1 runs over the Gaussians in INDEX order (no global depth sort), so
+// Two ways to reach depth order (gsr_set_binning; rasterizer.hip):
+//   global sort (default) dsort.hip's depth order of all P Gaussians, level 1 over it, and
+//                         tile_bin over the (already depth-ordered) SB lists.  Also what a
+//                         local-sort frame falls back to when an SB list is longer than the LDS
+//                         sort holds (kSortCap), and what deterministic mode uses (its backward
+//                         needs dsort's Gaussian-major record offsets).
+//   local sort (mode 0)   level 1 runs over the Gaussians in INDEX order (no global depth sort), so
 //                         every SB list is in id order; sb_sort_bin then sorts each SB's list by
-//                         depth inside LDS (stable LSD radix over the list's own key range: equal
-//                         depths keep id order) and bins it into the SB's tiles from LDS.  The
-//                         column scan publishes K and the longest SB list.
-//   global sort           dsort.hip's depth order of all P Gaussians, level 1 over it, and
-//                         tile_bin over the (already depth-ordered) SB lists: frames with an SB
-//                         list longer than the LDS sort holds (kSortCap), and deterministic mode
-//                         (whose backward needs dsort's Gaussian-major record offsets).
+//                         the raw depth bits of gs.dkey inside LDS (stable LSD radix over the list's
+//                         own key range: equal depths keep id order) and bins it into the SB's tiles
+//                         from LDS.  The column scan publishes K and the longest SB list.
 #include "gsr_launch.h"
 
 namespace gsr {

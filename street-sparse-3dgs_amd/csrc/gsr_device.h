@@ -657,7 +657,7 @@ __host__ __device__ __forceinline__ int cnt_col(const SBGrid &g, int chunk) {
 struct GeomState {          // per Gaussian, written by preprocess
     GRec *rec;
     uint32_t *tiles;        // tiles_touched
-    uint32_t *dkey;         // depth sort key: depth bits, 0xFFFFFFFF when culled (clobbered by the sort)
+    uint32_t *dkey;         // depth sort key: raw depth bits, 0xFFFFFFFF when culled (reordered by the sort)
     uint32_t *dkey_sorted;  // sort ping-pong buffer
     uint32_t *ids;          // sort ping-pong buffer (values)
     uint32_t *order;        // Gaussian ids in (depth, id) order
@@ -683,6 +683,7 @@ struct GeomState {          // per Gaussian, written by preprocess
     uint32_t *tb_flag;      // tile_bin split: per SB 1 = binned in slices; [nsb] = queued items
     uint32_t *tb_items;     // ... the slice items (kTBMaxItems: SB | slice << 12 | slices << 18)
     uint32_t *tb_cnt;       // ... per item and SB tile: the slice's instance count
+    uint32_t *ids2;         // sort ping-pong buffer (values): the third one a four-pass frame needs
 };
 // a 4-B packed rect (x0 | y0 << 8 | x1 << 16 | y1 << 24) in the 8-B form (x0 | y0 << 16, x1 | y1 << 16)
 __host__ __device__ __forceinline__ uint2 unpack_rect4(uint32_t q) {
@@ -707,8 +708,9 @@ __host__ __device__ __forceinline__ const uint32_t *drect4_of(const GeomState &g
 // predecessor segment gave up (both frames' images are NaN: the call fails); kHostFwdGiveUp: forward
 // workers gave up waiting for tile_order's ready word (the frame is completed exactly by the pool's
 // second launch; counted in gsr_forward_stats).
+// kHostWide: the depth sort's upsweep stores 1 here (before K) when the frame needed the fourth pass.
 enum HostWord { kHostK = 0, kHostErr = 1, kHostMaxSB = 2, kHostP1 = 3, kHostSBList = 4, kHostTileList = 5,
-                kHostFwdGiveUp = 6, kHostFwdErr = 7, kHostWords = 8 };
+                kHostFwdGiveUp = 6, kHostFwdErr = 7, kHostWide = 8, kHostWords = 9 };
 // The forward workers' bounded spins (render.hip fwd_seg_worker): `ready` = tile_order's release of
 // the queue, `flag` = a predecessor item's transmittance row; loop trips of ~256 / ~128 clocks.
 // gsr_set_fwd_spin_limits changes them (tests); `host` = the pinned words above.

@@ -95,9 +95,11 @@ void launch_gt_far_mask(int64_t P, const float *xyz, const GtGrid &g, float T, f
 int dsort_blocks(int P);
 size_t dsort_ctrl_words(int P);
 size_t dsort_ctrl_zero_words(int P);
+// host_wide (optional, pinned; with host_K, stored before it): 1 when a visible key lies outside the
+// three-pass window, so the frame's order came from the fourth pass.
 // host_err (optional, pinned): set with a system-scope store when a lookback spin gives up.
-void launch_depth_sort(int P, const GeomState &gs, uint32_t *host_K, uint32_t *host_err, hipStream_t s,
-                       hipEvent_t k_ready);
+void launch_depth_sort(int P, const GeomState &gs, uint32_t *host_K, uint32_t *host_wide, uint32_t *host_err,
+                       hipStream_t s, hipEvent_t k_ready);
 uint32_t *dsort_K_word(const GeomState &gs);
 uint32_t *dsort_err_word(const GeomState &gs);
 // a zeroed-per-frame control word the binning uses as a completion counter

@@ -208,7 +208,10 @@ int fail(int code, const std::string &msg) {
 std::atomic<int64_t> g_fwd_giveups{0}, g_kwait_ns{0};
 // frames whose forward ran with the forward split / the tile binning's superblock split armed
 std::atomic<int64_t> g_fsplit_frames{0}, g_tbsplit_frames{0};
-constexpr int kFwdStats = 8;
+// frames whose depth sort took the fourth pass (a visible depth outside the three-pass window); frames
+// completed by a sort pass queued after K was read (none: every frame queues its four launches)
+std::atomic<int64_t> g_sort_wide_frames{0}, g_sort_late_pass{0};
+constexpr int kFwdStats = 10;
 void collect_giveups() {
     if (!g_pinned) return;
     const uint32_t gu = __atomic_exchange_n(&g_pinned[kHostFwdGiveUp], 0u, __ATOMIC_SEQ_CST);
@@ -331,6 +334,7 @@ GeomState carve_geom(void *base, int P, int gx, int gy, size_t *bytes) {
     g.tb_flag = c.take<uint32_t>((size_t)g.sb.nsb + 1);
     g.tb_items = c.take<uint32_t>(kTBMaxItems);
     g.tb_cnt = c.take<uint32_t>((size_t)kTBMaxItems << (2 * g.sb.shift));
+    g.ids2 = c.take<uint32_t>(P);  // last: the arrays above keep their offsets
     if (bytes) *bytes = align_up(c.off, 256);
     return g;
 }
@@ -818,6 +822,7 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
         // deferred K: no event -- its marker packet cost a ~7 us gap before the first sort pass;
         // the host polls the pinned word the upsweep / column scan stores instead (read_K)
         k_ready = (defer && GSR_K_POLL) ? nullptr : g_k_ready[dev];
+        __atomic_store_n(&g_pinned[kHostWide], 0u, __ATOMIC_RELAXED);
         __atomic_store_n(&g_pinned[kHostK], kKPending, __ATOMIC_SEQ_CST);
     }
     const FrameWords fw_local{dsort_K_word(gs), dsort_maxsb_word(gs), g_pinned_dev};
@@ -837,7 +842,8 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
     } else if (P > 0) {
         {
             StageTimer st(1, s);
-            launch_depth_sort(P, gs, g_pinned_dev + kHostK, g_pinned_dev + kHostErr, s, k_ready);
+            launch_depth_sort(P, gs, g_pinned_dev + kHostK, g_pinned_dev + kHostWide, g_pinned_dev + kHostErr, s,
+                              k_ready);
         }
         if ((rc = check("depth sort", debug, s))) return rc;
     }
@@ -877,6 +883,9 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
                 return fail(GSR_ERR_DEVICE, "depth sort: a lookback spin timed out");
         }
         if ((rc = sticky_sort_error())) return rc;
+        // stored before K by the upsweep (0 on a local-sort frame and when K came from the device copy)
+        if (__atomic_load_n(&g_pinned[kHostWide], __ATOMIC_RELAXED))
+            g_sort_wide_frames.fetch_add(1, std::memory_order_relaxed);
         K = (int64_t)k;
         maxsb = local ? m : 0u;
         have_K = true;
@@ -892,7 +901,7 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
             return fail(GSR_ERR_DEVICE, "depth sort control reset failed");
         {
             StageTimer st(1, s);
-            launch_depth_sort(P, gs, nullptr, g_pinned_dev + kHostErr, s, nullptr);
+            launch_depth_sort(P, gs, nullptr, nullptr, g_pinned_dev + kHostErr, s, nullptr);
         }
         return check("depth sort", debug, s);
     };
@@ -1250,7 +1259,7 @@ int gsr_forward_stats(int64_t *out, int n) {
     collect_giveups();
     const int64_t v[kFwdStats] = {g_frames.load(), g_reruns.load(), g_local_frames.load(), g_fallbacks.load(),
                                   g_fwd_giveups.load(), g_kwait_ns.load(), g_fsplit_frames.load(),
-                                  g_tbsplit_frames.load()};
+                                  g_tbsplit_frames.load(), g_sort_wide_frames.load(), g_sort_late_pass.load()};
     int k = 0;
     for (; k < n && k < kFwdStats; k++) out[k] = v[k];
     return k;

@@ -159,11 +159,14 @@ def forward_stats() -> dict:
     """Frames rasterized since load, how many re-ran their binning at K, how many were binned by
     the local sort and how many of those fell back to the global sort, forward-split workers that
     gave up waiting for tile_order (their frames completed by the pool's second launch) and the host
-    nanoseconds spent waiting for K (gsr_forward_stats)."""
-    buf = (ctypes.c_int64 * 8)()
-    n = _L.gsr_forward_stats(buf, 8)
+    nanoseconds spent waiting for K, frames run with the forward / tile_bin split armed, frames whose depth
+    sort took the fourth pass (a visible depth outside the three-pass window, dsort.hip) and frames
+    completed by a sort pass queued late (always 0: four launches are queued for every frame)
+    (gsr_forward_stats)."""
+    buf = (ctypes.c_int64 * 10)()
+    n = _L.gsr_forward_stats(buf, 10)
     keys = ("frames", "reruns", "local_sort", "fallbacks", "fwd_worker_giveups", "k_wait_ns", "fwd_split_frames",
-            "tb_split_frames")
+            "tb_split_frames", "sort_wide_frames", "sort_late_pass")
     return {k: (int(buf[i]) if n > i else 0) for i, k in enumerate(keys)}
 
 

@@ -2,9 +2,11 @@
 // as one translation unit with the kernels (diagnostic stamps on):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DGSR_DS_TRACE \
 //         -I street-sparse-3dgs_amd/csrc -I include tools/dsort_bench.hip -o tools/dsort_bench
-//   tools/dsort_bench [P] [iters]
+//   tools/dsort_bench [P] [iters] [wide]
 // Synthetic keys: view depths z ~ U[2, 20] as float bits, 2% culled (0xFFFFFFFF); tile counts
-// 1..32; 8-B tile rects (rect4 unset: pass 3 gathers them, no rect carry).  Checks the order against std::stable_sort, the record offsets and K, then prints the
+// 1..32; 8-B tile rects (rect4 unset: the last pass gathers them, no rect carry).  wide = 1 puts 1% of
+// the keys outside the three-pass window (depths of 2e4..2e30 and, below the near plane, 1e-3..0.19),
+// so the frame takes the fourth pass.  Checks the order against std::stable_sort, the record offsets and K, then prints the
 // per-kernel HIP-event times and the per-workgroup phase stamps (median / max over workgroups,
 // relative to the kernel's first workgroup start).
 #include <algorithm>
@@ -31,13 +33,19 @@ using namespace gsr;
 int main(int argc, char **argv) {
     const int P = argc > 1 ? atoi(argv[1]) : 1000000;
     const int iters = argc > 2 ? atoi(argv[2]) : 20;
+    const bool wide = argc > 3 && atoi(argv[3]) != 0;
     std::mt19937 rng(7);
     std::uniform_real_distribution<float> uz(2.f, 20.f);
     std::uniform_int_distribution<int> ut(1, 32);
     std::vector<uint32_t> key(P), tiles(P);
     std::vector<GRec> rec(P);
     for (int i = 0; i < P; i++) {
-        const float z = uz(rng);
+        float z = uz(rng);
+        if (wide && (rng() % 100) == 0) {
+            const uint32_t r = rng();
+            z = (r & 1u) ? 2e4f * (float)(1u + (r >> 8) % 1000u) * ((r & 2u) ? 1e23f : 1.f)
+                         : 1e-3f + 0.189f * (float)((r >> 8) % 1000u) / 1000.f;
+        }
         const bool culled = (rng() % 50) == 0;
         key[i] = culled ? 0xFFFFFFFFu : __builtin_bit_cast(uint32_t, z);
         tiles[i] = culled ? 0u : (uint32_t)ut(rng);
@@ -51,6 +59,7 @@ int main(int argc, char **argv) {
     CK(hipMalloc(&gs.dkey, 4 * (size_t)P));
     CK(hipMalloc(&gs.dkey_sorted, 4 * (size_t)P));
     CK(hipMalloc(&gs.ids, 4 * (size_t)P));
+    CK(hipMalloc(&gs.ids2, 4 * (size_t)P));
     CK(hipMalloc(&gs.order, 4 * (size_t)P));
     CK(hipMalloc(&gs.offsets, 4 * (size_t)P));
     CK(hipMalloc(&gs.drect, 8 * (size_t)P));
@@ -80,23 +89,23 @@ int main(int argc, char **argv) {
         CK(hipMemsetAsync(trace, 0, 8ull * 5 * 4096 * 8, s));
         CK(hipEventRecord(ev[0], s));
         hipLaunchKernelGGL(dsort_upsweep_kernel, dim3(up_blocks(nb)), dim3(kDsThreads), 0, s, P, nb, gs.dkey, gs.tiles, gs.ctrl,
-                           (uint32_t *)nullptr);
+                           (uint32_t *)nullptr, (uint32_t *)nullptr);
         CK(hipEventRecord(ev[1], s));
-        hipLaunchKernelGGL(dsort_pass_kernel<0>, dim3(nb), dim3(kDsThreads), 0, s, P, nb, gs.dkey, gs.dkey_sorted,
-                           (const uint32_t *)nullptr, gs.ids, gs.ctrl, gs.offsets, gs.tiles, gs.rect8, (const uint32_t *)nullptr, gs.drect,
-                           (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
+        const uint32_t *const no_in = nullptr;
+        uint32_t *const no_out = nullptr;
+        hipLaunchKernelGGL(dsort_pass_kernel<0>, dim3(nb), dim3(kDsThreads), 0, s, P, nb, gs.dkey, gs.dkey_sorted, no_in,
+                           gs.ids, no_out, gs.ctrl, gs.offsets, gs.tiles, gs.rect8, no_in, gs.drect, no_in, no_out, no_out);
         CK(hipEventRecord(ev[2], s));
-        hipLaunchKernelGGL(dsort_pass_kernel<1>, dim3(nb), dim3(kDsThreads), 0, s, P, nb, gs.dkey_sorted, gs.dkey,
-                           gs.ids, gs.order, gs.ctrl, gs.offsets, gs.tiles, gs.rect8, (const uint32_t *)nullptr, gs.drect,
-                           (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(dsort_pass_kernel<1>, dim3(nb), dim3(kDsThreads), 0, s, P, nb, gs.dkey_sorted, gs.dkey, gs.ids,
+                           gs.ids2, no_out, gs.ctrl, gs.offsets, gs.tiles, gs.rect8, no_in, gs.drect, no_in, no_out, no_out);
         CK(hipEventRecord(ev[3], s));
-        hipLaunchKernelGGL(dsort_pass_kernel<2>, dim3(nb), dim3(kDsThreads), 0, s, P, nb, gs.dkey, gs.dkey_sorted,
-                           gs.order, gs.ids, gs.ctrl, gs.offsets, gs.tiles, gs.rect8, (const uint32_t *)nullptr, gs.drect,
-                           (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(dsort_pass_kernel<2>, dim3(nb), dim3(kDsThreads), 0, s, P, nb, gs.dkey, gs.dkey_sorted, gs.ids2,
+                           gs.ids, gs.order, gs.ctrl, gs.offsets, gs.tiles, gs.rect8, no_in, gs.drect, no_in, no_out,
+                           no_out);
         CK(hipEventRecord(ev[4], s));
-        hipLaunchKernelGGL(dsort_pass_kernel<3>, dim3(nb), dim3(kDsThreads), 0, s, P, nb, gs.dkey_sorted,
-                           (uint32_t *)nullptr, gs.ids, gs.order, gs.ctrl, gs.offsets, gs.tiles, gs.rect8, (const uint32_t *)nullptr, gs.drect,
-                           (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(dsort_pass_kernel<3>, dim3(nb), dim3(kDsThreads), 0, s, P, nb, gs.dkey_sorted, no_out, gs.ids,
+                           no_out, gs.order, gs.ctrl, gs.offsets, gs.tiles, gs.rect8, no_in, gs.drect, no_in, no_out,
+                           no_out);
         CK(hipEventRecord(ev[5], s));
         CK(hipStreamSynchronize(s));
         if (it >= 2)
@@ -114,19 +123,23 @@ int main(int argc, char **argv) {
     std::iota(want.begin(), want.end(), 0u);
     std::stable_sort(want.begin(), want.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
     size_t bad = 0;
-    for (int i = 0; i < P; i++) bad += order[i] != want[i];
+    // culled keys sort last and their slots are never written: the visible prefix is checked
+    const int Pv = (int)std::count_if(key.begin(), key.end(), [](uint32_t k) { return k != 0xFFFFFFFFu; });
+    for (int i = 0; i < Pv; i++) bad += order[i] != want[i];
     uint64_t run = 0, badoff = 0;
     for (int i = 0; i < P; i++)
         if (tiles[i]) {
             badoff += offs[i] != run;
             run += tiles[i];
         }
-    uint32_t K = 0;
+    uint32_t K = 0, wflag = 0;
     CK(hipMemcpy(&K, dsort_K_word(gs), 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(&wflag, gs.ctrl + kCtlWide, 4, hipMemcpyDeviceToHost));
+    bad += wflag != (wide ? 1u : 0u);
     std::vector<uint2> dr(P);
     CK(hipMemcpy(dr.data(), gs.drect, 8 * (size_t)P, hipMemcpyDeviceToHost));
-    for (int i = 0; i < P; i++) bad += dr[i].x != r8[want[i]].x || dr[i].y != r8[want[i]].y;
-    printf("P=%d blocks=%d  order mismatches=%zu  offset mismatches=%llu  K=%u (want %llu)\n", P, nb, bad,
+    for (int i = 0; i < Pv; i++) bad += dr[i].x != r8[want[i]].x || dr[i].y != r8[want[i]].y;
+    printf("P=%d blocks=%d wide=%u  order mismatches=%zu  offset mismatches=%llu  K=%u (want %llu)\n", P, nb, wflag, bad,
            (unsigned long long)badoff, K, (unsigned long long)run);
     const char *names[5] = {"upsweep", "pass0", "pass1", "pass2", "pass3"};
     for (int k = 0; k < 5; k++) printf("%-8s %8.2f us\n", names[k], 1e3 * tk[k] / iters);
