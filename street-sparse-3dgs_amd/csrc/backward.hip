@@ -261,30 +261,12 @@ __global__ __launch_bounds__(256) void record_sum_kernel(int P, int gx, const fl
 }
 
 constexpr int kShPitch = 13;  // padded LDS row pitch (float4) of the staged SH rows
-#ifndef GSR_BWD_NT
-#define GSR_BWD_NT 1  // gradient rows written with non-temporal stores (streamed once, never re-read here)
-#endif
-#ifndef GSR_ACC_LD_NT
-#define GSR_ACC_LD_NT 0  // measured: non-temporal accumulator loads slow preprocess_bwd (82 -> 85 us)
-#endif
-__device__ __forceinline__ float4 ld_acc(const float4 *p) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    if (!GSR_ACC_LD_NT) return *p;
-    const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(p));
-    return make_float4(t.x, t.y, t.z, t.w);
-}
-__device__ __forceinline__ void st_out(float *p, float v) {
-    if (GSR_BWD_NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
+// gradient rows are written with non-temporal stores (streamed once, never re-read here)
+__device__ __forceinline__ void st_out(float *p, float v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ void st_out(float4 *p, float4 v) {
     typedef float f4 __attribute__((ext_vector_type(4)));
-    if (GSR_BWD_NT) __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4 *>(p));
-    else *p = v;
+    __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4 *>(p));
 }
-#ifndef GSR_BWD_SKIP_DEAD
-#define GSR_BWD_SKIP_DEAD 1
-#endif
 
 // The chain rule of one live Gaussian's geometry (its ten accumulated sums g): conic -> 2D
 // covariance -> (3D covariance, mean) through the EWA Jacobian, screen-space mean -> mean3D
@@ -448,8 +430,7 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
     if (sc.atomic) {
         // render_bwd's atomic accumulator row (zeroed by render_fwd; untouched rows stay zero)
         // the rows are dead after this read: non-temporal loads keep them out of the caches
-        const float4 a0 = ld_acc(sc.acc + 4 * (size_t)iv), a1 = ld_acc(sc.acc + 4 * (size_t)iv + 1),
-                     a2 = ld_acc(sc.acc + 4 * (size_t)iv + 2);
+        const float4 a0 = sc.acc[4 * (size_t)iv], a1 = sc.acc[4 * (size_t)iv + 1], a2 = sc.acc[4 * (size_t)iv + 2];
         g[0] = a0.x; g[1] = a0.y; g[2] = a0.z; g[3] = a0.w;
         g[4] = a1.x; g[5] = a1.y; g[6] = a1.z; g[7] = a1.w;
         g[8] = a2.x; g[9] = a2.y;
@@ -491,10 +472,8 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
 #pragma unroll
             for (int q = 0; q < 4; q++) a[q] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        if (GSR_BWD_SKIP_DEAD) {
-            if (!sc.atomic && vis) nz = nz || out.dopacity[i] != 0.f;  // record mode: summed by record_sum
-            live = vis && nz;
-        }
+        if (!sc.atomic && vis) nz = nz || out.dopacity[i] != 0.f;  // record mode: summed by record_sum
+        live = vis && nz;
     }
     // sparse rows (the native train step): the liveness column; a dead row's other gradient rows
     // are not written
@@ -661,8 +640,7 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
 // with the screen-space mean and opacity gradients it wrote; zero for an invisible Gaussian.
 __device__ __forceinline__ void load_sums(const BwdScratch &sc, const GaussianGrads &out, int i, bool vis, float g[10]) {
     if (sc.atomic) {
-        const float4 a0 = ld_acc(sc.acc + 4 * (size_t)i), a1 = ld_acc(sc.acc + 4 * (size_t)i + 1),
-                     a2 = ld_acc(sc.acc + 4 * (size_t)i + 2);
+        const float4 a0 = sc.acc[4 * (size_t)i], a1 = sc.acc[4 * (size_t)i + 1], a2 = sc.acc[4 * (size_t)i + 2];
         g[0] = a0.x; g[1] = a0.y; g[2] = a0.z; g[3] = a0.w;
         g[4] = a1.x; g[5] = a1.y; g[6] = a1.z; g[7] = a1.w;
         g[8] = a2.x; g[9] = a2.y;
@@ -679,13 +657,8 @@ __device__ __forceinline__ void load_sums(const BwdScratch &sc, const GaussianGr
         for (int k = 0; k < 10; k++) g[k] = 0.f;
 }
 
-#ifndef GSR_GRAD_WIDE
-#define GSR_GRAD_WIDE 0  // 1: float4 stores of whole waves' 3-float rows; measured slower (r03k: 0.0943 vs 0.0901 ms)
-#endif
-__device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 __global__ __launch_bounds__(256) void grad_rows_kernel(int P, const int *__restrict__ radii, BwdScratch sc,
-                                                        GaussianGrads out, int zero_dead) {
+                                                        GaussianGrads out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & (kWave - 1);
     const bool valid = i < P;
@@ -700,26 +673,13 @@ __global__ __launch_bounds__(256) void grad_rows_kernel(int P, const int *__rest
     const uint64_t lm = __ballot(live);
     if (lane == 0 && (i >> 6) < (P + 63) / 64) sc.live[i >> 6] = lm;
     const int64_t row0 = (int64_t)i - lane;
-    // GSR_GRAD_WIDE: a full wave's 3-float rows (768 B per array) go out as 48 float4 stores instead
-    // of three strided dword stores per lane -- the mean2D values staged through a wave-private LDS
-    // row, the zero rows of means3D / scales written as float4s wherever no live row shares them
-    const bool wide = GSR_GRAD_WIDE && row0 + kWave <= P && aligned16(out.dmeans2D) && aligned16(out.dmeans3D) &&
-                      aligned16(out.dscales);
-    __shared__ __attribute__((aligned(16))) float s_m2[256 / kWave][3 * kWave];
-    float *m2 = s_m2[threadIdx.x >> 6];
     if (valid) {
         const float c2 = out.sparse_rows && live ? 1.f : 0.f;
-        if (wide && sc.atomic) {
-            m2[3 * lane + 0] = g[0];
-            m2[3 * lane + 1] = g[1];
-            m2[3 * lane + 2] = c2;
-        } else {
-            if (sc.atomic) {  // record mode: written by record_sum_kernel
-                st_out(&out.dmeans2D[3 * i + 0], g[0]);
-                st_out(&out.dmeans2D[3 * i + 1], g[1]);
-            }
-            if (sc.atomic || out.sparse_rows) st_out(&out.dmeans2D[3 * i + 2], c2);
+        if (sc.atomic) {  // record mode: written by record_sum_kernel
+            st_out(&out.dmeans2D[3 * i + 0], g[0]);
+            st_out(&out.dmeans2D[3 * i + 1], g[1]);
         }
+        if (sc.atomic || out.sparse_rows) st_out(&out.dmeans2D[3 * i + 2], c2);
         if (sc.atomic) st_out(&out.dopacity[i], g[5]);
         if (out.dcolors) {
             out.dcolors[3 * i + 0] = 0.f;
@@ -730,35 +690,9 @@ __global__ __launch_bounds__(256) void grad_rows_kernel(int P, const int *__rest
 #pragma unroll
             for (int k = 0; k < 6; k++) out.dcov3D[6 * i + k] = 0.f;
     }
-    if (wide && sc.atomic) {
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the wave's LDS row is complete
-        __builtin_amdgcn_wave_barrier();
-        if (lane < 48) {
-            const float4 v = *reinterpret_cast<const float4 *>(m2 + 4 * lane);
-            st_out(reinterpret_cast<float4 *>(out.dmeans2D + 3 * row0) + lane, v);
-        }
-    }
-    if (out.sparse_rows || !zero_dead) return;
+    if (out.sparse_rows) return;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (wide) {
-        if (lane < 48) {
-            // floats 4 lane .. 4 lane + 3 of the wave's rows: rows 4 lane / 3 and (4 lane + 3) / 3
-            const int ra = (4 * lane) / 3, rb = (4 * lane + 3) / 3;
-            float4 *m3 = reinterpret_cast<float4 *>(out.dmeans3D + 3 * row0) + lane;
-            float4 *sc3 = reinterpret_cast<float4 *>(out.dscales + 3 * row0) + lane;
-            if (!(((lm >> ra) | (lm >> rb)) & 1ull)) {
-                st_out(m3, z4);
-                st_out(sc3, z4);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; e++)
-                    if (!((lm >> ((4 * lane + e) / 3)) & 1ull)) {
-                        st_out(reinterpret_cast<float *>(m3) + e, 0.f);
-                        st_out(reinterpret_cast<float *>(sc3) + e, 0.f);
-                    }
-            }
-        }
-    } else if (valid && !live) {
+    if (valid && !live) {
         st_out(&out.dmeans3D[3 * i + 0], 0.f);
         st_out(&out.dmeans3D[3 * i + 1], 0.f);
         st_out(&out.dmeans3D[3 * i + 2], 0.f);
@@ -1026,22 +960,13 @@ __global__ __launch_bounds__(256) void grad_live_kernel(LiveArgs a, uint32_t *__
     }
 }
 
-#ifndef GSR_BWD_ZERO_IN_RENDER
-#define GSR_BWD_ZERO_IN_RENDER 1  // the dense zero rows stored by render_bwd's waves after their replay
-#endif
 #ifndef GSR_BWD_ZERO_PCT
 #define GSR_BWD_ZERO_PCT 100
-#endif
-#ifndef GSR_BWD_MEMSET
-#define GSR_BWD_MEMSET 0  // 1: hipMemsetAsync fills; preprocess_bwd 0.0891 -> 0.0866 ms but the fills leave dirty lines that slow the next frame (preprocess 0.035 -> 0.040, sort 0.106 -> 0.111 ms; r03n)
-#endif
-#ifndef GSR_BWD_SPLIT
-#define GSR_BWD_SPLIT 1  // 0: the single preprocess_bwd_kernel for every frame
 #endif
 
 namespace {
 bool split_ok(const GaussianInputs &in, const GaussianGrads &out, const BwdScratch &sc) {
-    return GSR_BWD_SPLIT && GSR_BWD_SKIP_DEAD && sc.live && in.shs && in.M == 16 && !in.cov3D_precomp && in.scales &&
+    return sc.live && in.shs && in.M == 16 && !in.cov3D_precomp && in.scales &&
            in.rotations && reinterpret_cast<uintptr_t>(in.shs) % 16 == 0 &&
            reinterpret_cast<uintptr_t>(out.dsh) % 16 == 0;
 }
@@ -1049,7 +974,7 @@ bool split_ok(const GaussianInputs &in, const GaussianGrads &out, const BwdScrat
 
 bool bwd_zero_rows(const GaussianInputs &in, const GaussianGrads &out, const BwdScratch &sc, uint32_t *gs_stamps,
                    int nblocks, ZeroRows *z) {
-    if (!GSR_BWD_ZERO_IN_RENDER || in.P == 0 || nblocks <= 0 || !sc.atomic || !gs_stamps || !split_ok(in, out, sc))
+    if (in.P == 0 || nblocks <= 0 || !sc.atomic || !gs_stamps || !split_ok(in, out, sc))
         return false;
     // sparse rows: only the screen-space mean and opacity gradients are dense
     const uint64_t P = (uint64_t)in.P;
@@ -1079,7 +1004,7 @@ void launch_preprocess_bwd(const GaussianInputs &in, const Camera &cam, const Ge
                            const ZeroRows *zr) {
     const bool rows_zeroed = zr != nullptr;
     if (in.P == 0) return;
-    if (!sc.atomic)  // atomic mode: the sums are already in GeomState.acc
+    if (!sc.atomic)  // atomic mode: the sums are already in sc.acc
         hipLaunchKernelGGL(record_sum_kernel, dim3((in.P + 255) / 256), dim3(256), 0, s, in.P, cam.gx, in.means3D,
                        cam.view, gs.rect8, gs.rect4, gs.offsets, is.boundary, sc, out.dmeans2D, out.dopacity);
     const bool split = split_ok(in, out, sc);
@@ -1088,21 +1013,10 @@ void launch_preprocess_bwd(const GaussianInputs &in, const Camera &cam, const Ge
     StepAct act = step_act();
     if (!in.raw || !out.sparse_rows) act.on = 0;
     if (split) {
-        // dense rows: the dead rows' zeros as one fill per gradient array (streaming stores of whole
-        // arrays) instead of grad_rows_kernel's per-row stores; grad_live_kernel then overwrites the
-        // live rows (GSR_BWD_MEMSET=0: grad_rows_kernel writes the zeros)
-        const bool fill = GSR_BWD_MEMSET && !out.sparse_rows && !rows_zeroed;
-        if (fill) {
-            const size_t P = (size_t)in.P;
-            (void)hipMemsetAsync(out.dsh, 0, sizeof(float) * P * 48, s);
-            (void)hipMemsetAsync(out.dmeans3D, 0, sizeof(float) * P * 3, s);
-            (void)hipMemsetAsync(out.dscales, 0, sizeof(float) * P * 3, s);
-            (void)hipMemsetAsync(out.drots, 0, sizeof(float) * P * 4, s);
-        }
-        // rows zeroed by render_bwd: its stamps name the live rows (no grad_rows pass)
+        // rows zeroed by render_bwd: its stamps name the live rows (no grad_rows pass); otherwise
+        // grad_rows_kernel writes the dead rows' zeros
         if (!rows_zeroed)
-            hipLaunchKernelGGL(grad_rows_kernel, dim3((in.P + 255) / 256), dim3(256), 0, s, in.P, radii, sc, out,
-                               fill ? 0 : 1);
+            hipLaunchKernelGGL(grad_rows_kernel, dim3((in.P + 255) / 256), dim3(256), 0, s, in.P, radii, sc, out);
         const LiveArgs la{in.P, in.D, in.means3D, in.shs, gs.clamped, in.scales, in.rotations, in.scale_modifier,
                           true_scale_gradient() ? in.scale_modifier : 1.0f, cam.view, cam.proj, cam.campos, cam.tanx,
                           cam.tany, cam.fx, cam.fy, sc, out, in.raw, rows_zeroed ? 1 : 0, act};

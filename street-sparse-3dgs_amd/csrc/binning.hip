@@ -204,8 +204,6 @@ __global__ __launch_bounds__(kColThreads) void sb_colscan_kernel(SBGrid sg, uint
                                                                  uint32_t *__restrict__ base_g,
                                                                  uint32_t *__restrict__ base_i,
                                                                  uint32_t *__restrict__ done, FrameWords fw,
-                                                                 uint32_t *__restrict__ sb_order,
-                                                                 uint32_t *__restrict__ zero_classes,
                                                                  uint32_t *__restrict__ tb_flag,
                                                                  uint32_t *__restrict__ tb_items, uint32_t tb_len,
                                                                  uint32_t *__restrict__ host_sblist, int P,
@@ -213,8 +211,6 @@ __global__ __launch_bounds__(kColThreads) void sb_colscan_kernel(SBGrid sg, uint
     GSR_KS(kKsSbColscan);
     __shared__ uint32_t wsum[kColThreads / 64];
     __shared__ uint32_t s_last, s_tb;
-    __shared__ uint32_t s_ci[GSR_FWD_SB_ORDER ? kMaxSB : 1];  // last workgroup: SB instance totals
-    __shared__ uint32_t s_hist[GSR_FWD_SB_ORDER ? 256 : 1];
     const int s = blockIdx.x;
     uint32_t *row = cnt_g + (size_t)s * sg.ccols;
     const uint32_t *rowi = cnt_i + (size_t)s * sg.ccols;
@@ -260,7 +256,6 @@ __global__ __launch_bounds__(kColThreads) void sb_colscan_kernel(SBGrid sg, uint
                 tb_items[at + j] = fits ? ((uint32_t)k | j << 12 | nsl << 18) : kTBVoid;
             tb_flag[k] = fits ? 1u : 0u;
         }
-        if (GSR_FWD_SB_ORDER && k < nsb) s_ci[k] = vi;
         uint32_t tg, ti;
         const uint32_t eg = block_exclusive_scan<kColThreads>(vg, wsum, tg);
         const uint32_t ei = block_exclusive_scan<kColThreads>(vi, wsum, ti);
@@ -279,39 +274,6 @@ __global__ __launch_bounds__(kColThreads) void sb_colscan_kernel(SBGrid sg, uint
         __syncthreads();
         if (threadIdx.x == 0) tb_flag[nsb] = min(s_tb, (uint32_t)kTBMaxItems);
     }
-    if (zero_classes && threadIdx.x < kBwdClasses) zero_classes[threadIdx.x] = 0u;
-    if (zero_classes && threadIdx.x == 0) zero_classes[kBwdSegCount] = 0u;
-    if (GSR_FWD_SB_ORDER && sb_order) {
-        // the forward's launch order, heaviest first: SBs bucketed into 256 descending classes of
-        // their mean tile list length (16 instances per class), in order of the bucket scan
-        const int tshift = 2 * sg.shift;
-        const auto cls = [&](int k) {
-            const uint32_t c = (s_ci[k] >> tshift) >> 4;
-            return 255u - (c < 255u ? c : 255u);
-        };
-        s_hist[threadIdx.x] = 0u;  // kColThreads == 256
-        __syncthreads();
-        for (int k = threadIdx.x; k < nsb; k += kColThreads) atomicAdd(&s_hist[cls(k)], 1u);
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            const int l = threadIdx.x;
-            const uint32_t a = s_hist[4 * l], b = s_hist[4 * l + 1], c = s_hist[4 * l + 2], d = s_hist[4 * l + 3];
-            const uint32_t sum = a + b + c + d;
-            uint32_t incl = sum;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t v = (uint32_t)__shfl_up((int)incl, o, 64);
-                if (l >= o) incl += v;
-            }
-            const uint32_t ex = incl - sum;
-            s_hist[4 * l] = ex;
-            s_hist[4 * l + 1] = ex + a;
-            s_hist[4 * l + 2] = ex + a + b;
-            s_hist[4 * l + 3] = ex + a + b + c;
-        }
-        __syncthreads();
-        for (int k = threadIdx.x; k < nsb; k += kColThreads) sb_order[atomicAdd(&s_hist[cls(k)], 1u)] = (uint32_t)k;
-    }
     if (fw.dev_K || host_sblist) {
         // the longest SB list: for the split gate's hint (host_sblist), and on local-sort frames K
         // (= the instance total) and that maximum for the kernels and the host.  The host's K word
@@ -322,10 +284,7 @@ __global__ __launch_bounds__(kColThreads) void sb_colscan_kernel(SBGrid sg, uint
         __syncthreads();
         if (threadIdx.x == 0) {
             for (int k = 1; k < kColThreads / 64; k++) mg = max(mg, wsum[k]);
-            if (host_sblist) {
-                if (GSR_HOST_WORDS == 2) *host_sblist = mg;  // a device word render_fwd forwards
-                else __hip_atomic_store(host_sblist, mg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            if (host_sblist) __hip_atomic_store(host_sblist, mg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
     if (fw.dev_K) {
@@ -1031,14 +990,14 @@ SBGrid sb_grid(int gx, int gy, int P) {
     g.nchunks = (P + g.chunk - 1) / g.chunk;
     if (g.nchunks < 1) g.nchunks = 1;
     g.cper = sb_blocks(g) / 8 + (sb_blocks(g) % 8 != 0);
-    g.ccols = GSR_CNT_XCD ? 8 * g.cper : g.nchunks;
+    g.ccols = 8 * g.cper;
     return g;
 }
 
 bool sb_grid_supported(const SBGrid &g) { return g.nsb <= kMaxSB; }
 
 void launch_binning_count(int P, const Camera &cam, const GeomState &gs, bool index_order, const FrameWords &fw,
-                          uint32_t *sb_order, uint32_t *zero_classes, hipStream_t s, uint32_t tb_split,
+                          hipStream_t s, uint32_t tb_split,
                           uint32_t *host_sblist) {
     const SBGrid &sg = gs.sb;
     if (P == 0 || cam.gx * cam.gy == 0) return;
@@ -1049,7 +1008,7 @@ void launch_binning_count(int P, const Camera &cam, const GeomState &gs, bool in
     hipLaunchKernelGGL(sb_count_kernel, dim3(sb_blocks(sg)), dim3(1024), l1, s, P, sg, rects, rects4, gs.sb_cnt_g,
                        gs.sb_cnt_i, culled);
     hipLaunchKernelGGL(sb_colscan_kernel, dim3(sg.nsb), dim3(kColThreads), 0, s, sg, gs.sb_cnt_g, gs.sb_cnt_i,
-                       gs.sb_base_g, gs.sb_base_i, dsort_aux_word(gs), fw, sb_order, zero_classes,
+                       gs.sb_base_g, gs.sb_base_i, dsort_aux_word(gs), fw,
                        index_order ? nullptr : gs.tb_flag, gs.tb_items, tb_split, host_sblist, P, culled);
 }
 

@@ -70,7 +70,7 @@ constexpr int kCtlErr = 6;     // set when a bounded spin gave up (never expecte
 constexpr int kCtlAux = 7;     // per-frame counter lent to the binning (sb_colscan's last-workgroup count)
 constexpr int kCtlMaxSB = 8;   // local-sort frames: the longest SB list (sb_colscan)
 constexpr int kCtlFwdReady = 9;  // the forward split's queue released by tile_order (workers launched ahead)
-constexpr int kCtlLongest = 10;  // [2]: the frame's longest tile list and superblock list (split gate hints)
+constexpr int kCtlSpare = 10;    // [2]: unused (the words after it keep their places)
 constexpr int kCtlCulled = 12;   // culled Gaussians (key 0xFFFFFFFF): the depth order's last P - visible slots
 constexpr int kCtlLive = 13;     // [2]: the backward's live-row list length and finished workgroups (backward.hip;
                                  // zeroed again by grad_live_kernel's last workgroup)
@@ -121,12 +121,9 @@ __device__ uint64_t *g_ds_trace;
 #define DS_STAMP_AFTER(kern, slot, x) DS_STAMP(kern, slot)
 #endif
 
-// GSR_DSORT_CARRY: with 4-B rects, the tile rect travels with the Gaussian id through the
+// Rect carry: with 4-B rects, the tile rect travels with the Gaussian id through the
 // passes (read coalesced by pass 0 in index order, ping-ponged through the idle rect8 array), so
 // the last pass stores it instead of gathering rect4[id] -- one random 64-B line per Gaussian.
-#ifndef GSR_DSORT_CARRY
-#define GSR_DSORT_CARRY 1
-#endif
 
 constexpr uint32_t kFlagAgg = 1u << 30, kFlagInc = 2u << 30, kCountMask = (1u << 30) - 1u;
 
@@ -323,12 +320,12 @@ __global__ __launch_bounds__(kDsThreads) void dsort_pass_kernel(int P, int nb, c
     const bool wide = kPass >= 2 && ctl[kCtlWide] != 0u;  // the upsweep's, complete before any pass starts
     if (kPass == kPasses - 1 && !wide) return;            // pass 2 was the last
     const bool last = kPass == kPasses - 1 || (kPass == kPasses - 2 && !wide);
-    // rect carry (GSR_DSORT_CARRY): pass 0 reads rect4 itself, the others rin; the last pass stores
-    // into drect's 4-B form, the others into rout
-    const bool carry = GSR_DSORT_CARRY && rect4 != nullptr;
+    // rect carry: pass 0 reads rect4 itself, the others rin; the last pass stores into drect's 4-B
+    // form, the others into rout
+    const bool carry = rect4 != nullptr;
     __shared__ uint32_t s_key[kDsTile];
     __shared__ uint32_t s_val[kDsTile];
-    __shared__ uint32_t s_rc[GSR_DSORT_CARRY ? kDsTile : 1];  // carried rects
+    __shared__ uint32_t s_rc[kDsTile];  // carried rects
     __shared__ uint32_t s_wh[kDsWaves][kRadix];  // per-wave digit counts -> exclusive prefix over waves
     __shared__ __attribute__((aligned(16))) uint32_t s_gb[kRowSets][kRadix];  // global digit base (partial sums, then [0] scanned)
     __shared__ uint32_t s_bex[kRadix];           // tile-local digit base
@@ -499,7 +496,7 @@ __global__ __launch_bounds__(kDsThreads) void dsort_pass_kernel(int P, int nb, c
             const uint32_t lp = s_bex[d] + s_wh[w][d] + rk[k];
             s_key[lp] = key[k];
             s_val[lp] = kFirst ? (uint32_t)tile0 + (uint32_t)i : val[k];
-            if (GSR_DSORT_CARRY && carry) s_rc[lp] = rc[k];
+            if (carry) s_rc[lp] = rc[k];
         }
     }
     DS_STAMP(1 + kPass, 7);
@@ -550,17 +547,12 @@ __global__ __launch_bounds__(kDsThreads) void dsort_pass_kernel(int P, int nb, c
         const uint32_t g = s_val[i];
         if (last) {
             order[j] = g;
-            if (GSR_DSORT_CARRY && carry) {
-                reinterpret_cast<uint32_t *>(drect)[j] = s_rc[i];  // drect4_of(gs), carried
-            } else if (rect4) {
-                reinterpret_cast<uint32_t *>(drect)[j] = rect4[g];  // drect4_of(gs)
-            } else {
-                drect[j] = rect8[g];
-            }
+            if (carry) reinterpret_cast<uint32_t *>(drect)[j] = s_rc[i];  // drect4_of(gs), carried
+            else drect[j] = rect8[g];
         } else {
             kout[j] = k;
             vout[j] = g;
-            if (GSR_DSORT_CARRY && carry) rout[j] = s_rc[i];
+            if (carry) rout[j] = s_rc[i];
         }
     }
     DS_STAMP(1 + kPass, 4);
@@ -602,7 +594,6 @@ uint32_t *dsort_err_word(const GeomState &gs) { return gs.ctrl + kCtlErr; }
 uint32_t *dsort_aux_word(const GeomState &gs) { return gs.ctrl + kCtlAux; }
 uint32_t *dsort_maxsb_word(const GeomState &gs) { return gs.ctrl + kCtlMaxSB; }
 uint32_t *dsort_fwdready_word(const GeomState &gs) { return gs.ctrl + kCtlFwdReady; }
-uint32_t *dsort_longest_words(const GeomState &gs) { return gs.ctrl + kCtlLongest; }
 uint32_t *dsort_culled_word(const GeomState &gs) { return gs.ctrl + kCtlCulled; }
 uint32_t *dsort_live_words(const GeomState &gs) { return gs.ctrl + kCtlLive; }
 int dsort_head_words() { return kCtlHead; }

@@ -540,19 +540,10 @@ struct SBGrid {
     int shift, nsbx, nsby, nsb, nchunks, chunk;  // chunk: depth-ordered Gaussians per level-1 chunk
     int cper, ccols;                             // counter columns per XCD, row stride of the counters
 };
-// GSR_BWD_CLS: render_fwd's workgroups place their tile in one of kBwdClasses backward work
-// classes (a counter atomic) and render_bwd's workgroups find their tile from the class counts --
-// the backward launch order without a tile_order launch between the forward and the backward
-#ifndef GSR_BWD_CLS
-#define GSR_BWD_CLS 1
-#endif
+// render_fwd's workgroups place their tile in one of kBwdClasses backward work classes (a counter
+// atomic) and render_bwd's workgroups find their tile from the class counts -- the backward launch
+// order without a tile_order launch between the forward and the backward
 constexpr int kBwdClasses = 256;
-// GSR_FWD_SB_ORDER: the forward's launch order is by superblock (heaviest SB first, by its mean
-// tile-instance count; an SB's tiles consecutive), bucketed by the level-1 column scan's last
-// workgroup -- no tile_order launch between the tile binning and render_fwd
-#ifndef GSR_FWD_SB_ORDER
-#define GSR_FWD_SB_ORDER 0  // measured slower: render_fwd +11.5 us for the 10-us launch it saves (r03z)
-#endif
 constexpr int kBwdClassShift = 2;  // class = 255 - min(work >> 2, 255): heaviest first
 
 // Backward segments (gsr_set_bwd_segment): a tile whose backward work (last contributor position)
@@ -592,7 +583,6 @@ constexpr uint32_t kMinFwdSeg = 1024;
 #define GSR_FSEG_FACTOR 6
 #endif
 __host__ __device__ __forceinline__ bool fseg_splits(uint32_t len, uint32_t fseg_min) { return fseg_min && len > fseg_min; }
-constexpr int kFwdWorkers = 256;      // the in-kernel variant's pool (GSR_FWD_SEG_INKERNEL)
 // render_fwd_seg_kernel's pool, launched ahead of tile_order: street views with 300k+ lists 1.40 /
 // 1.59 ms render_fwd at 256, 1.24 / 1.28 at 512, 1.24 / 1.27 at 1024 (r04zd)
 constexpr int kFwdPoolWorkers = 512;
@@ -624,12 +614,6 @@ __host__ __device__ __forceinline__ FwdSegLayout fseg_layout(void *bin_base, int
     return f;
 }
 
-#ifndef GSR_RECT4
-#define GSR_RECT4 1
-#endif
-#ifndef GSR_CNT_XCD
-#define GSR_CNT_XCD 1
-#endif
 // Counter column of a level-1 chunk.  Chunk c runs as workgroup c, and workgroups are dealt to
 // the 8 XCDs round-robin, so the columns of one XCD's chunks are made adjacent: its 4-B counter
 // stores then fill whole lines in its own L2 instead of sharing every line with the 7 other XCDs.
@@ -649,7 +633,6 @@ __host__ __device__ __forceinline__ int sb_blocks(const SBGrid &g) {
     return kXcdGroup == 1 ? g.nchunks : (g.nchunks + 8 * kXcdGroup - 1) / (8 * kXcdGroup) * 8 * kXcdGroup;
 }
 __host__ __device__ __forceinline__ int cnt_col(const SBGrid &g, int chunk) {
-    if (!GSR_CNT_XCD) return chunk;
     if (kXcdGroup == 1) return (chunk & 7) * g.cper + (chunk >> 3);
     return ((chunk / kXcdGroup) & 7) * g.cper + (chunk / (8 * kXcdGroup)) * kXcdGroup + chunk % kXcdGroup;
 }
@@ -677,8 +660,6 @@ struct GeomState {          // per Gaussian, written by preprocess
     uint32_t *sb_cnt_i;
     uint32_t *sb_base_g;
     uint32_t *sb_base_i;
-    float4 *acc;            // backward accumulators, 4 float4 (64 B) per Gaussian, zeroed by render_fwd
-    int nacc;               // rows of acc (P)
     uint32_t *live_stamp;   // per Gaussian: the stamp of the last backward whose render_bwd staged it
     uint32_t *tb_flag;      // tile_bin split: per SB 1 = binned in slices; [nsb] = queued items
     uint32_t *tb_items;     // ... the slice items (kTBMaxItems: SB | slice << 12 | slices << 18)
@@ -699,9 +680,6 @@ __host__ __device__ __forceinline__ const uint32_t *drect4_of(const GeomState &g
 // the pinned host words the host waits on.  host[kHostK] is stored last.
 // kHostSBList / kHostTileList: every frame's longest superblock list (sb_colscan) and longest tile
 // list (the forward's tile_order), read by the host as the split gate's hint (rasterizer.hip)
-#ifndef GSR_HOST_WORDS
-#define GSR_HOST_WORDS 1  // split gate hints: 1 stored by tile_order / sb_colscan, 2 forwarded by render_fwd, 0 none (A/B)
-#endif
 // Sticky flags the kernels set with plain system-scope stores (read-modify-write atomics on pinned host
 // memory need PCIe atomics, which a host may not have) and the host's next call takes:
 // kHostErr: a depth-sort lookback spin gave up; kHostFwdErr: a forward worker's wait for a
@@ -742,8 +720,7 @@ struct ImageState {
     uint32_t *n_contrib;    // per pixel: 1-based list position of the last contributor
     uint32_t *tile_work;    // per tile: backward work (last contributor position, max over pixels)
     uint32_t *tile_ids;     // forward launch order (tiles by descending list length)
-    uint32_t *tile_order;   // backward launch order (tiles by descending tile_work; GSR_BWD_CLS = 0)
-    uint32_t *bwd_cnt;      // GSR_BWD_CLS: per backward work class, the tiles render_fwd placed in it
+    uint32_t *bwd_cnt;      // per backward work class, the tiles render_fwd placed in it
     uint32_t *bwd_cls;      // ... and those tiles, class c at [c * T, c * T + bwd_cnt[c])
 };
 
@@ -754,11 +731,11 @@ struct ImageState {
 //
 // Default (atomic) mode: no records; render_bwd adds each live instance's ten values (same order:
 // dmean2D x, y, dconic a, b, c, dopacity, drgb r, g, b, dinvdepth) into the Gaussian's 64-B
-// accumulator row GeomState.acc with no-return float atomics, one 40-B segment per instance.
+// accumulator row (BwdScratch.acc) with no-return float atomics, one 40-B segment per instance.
 struct BwdScratch {
     float4 *rec;
     float4 *gsum;  // per Gaussian: {dconic a, b, c, dinvdepth}, {drgb r, g, b, 0} (record_sum -> preprocess_bwd)
-    float4 *acc;   // atomic mode: GeomState.acc (rec / gsum unused)
+    float4 *acc;   // atomic mode: the device's persistent accumulator rows (rasterizer.hip acc_rows; rec / gsum unused)
     uint64_t *live;  // atomic mode: one mask of live rows (nonzero sums) per 64 Gaussians (backward.hip)
     uint32_t *list;  // the live rows, grad_live_list_kernel -> grad_live_kernel (P entries)
     int atomic;

@@ -47,13 +47,13 @@ bool color_split_supported(const GaussianInputs &in);
 // blocks > 0: a persistent grid of that many blocks (the pass held to part of the chip)
 void launch_preprocess_color(const GaussianInputs &in, const Camera &cam, const GeomState &gs, const int *radii,
                              hipStream_t s, int blocks = 0);
-// render.hip: tiles ordered heaviest first by work[t] (or, with work == NULL, by list length).
+// render.hip: the forward's launch order, tiles by descending list length; zero_classes != NULL: the
+// backward class counters render_fwd fills are zeroed.
 // fctl != NULL and fseg_len != 0: also the forward segments' item queue (FwdSegLayout in the
 // binning buffer at bin_base; fctl = bwd_cnt + kFwdItemsWord).
-void launch_tile_order(const uint32_t *work, const uint2 *ranges, int T, int shift, uint32_t *order, hipStream_t s,
-                       const uint32_t *kdev = nullptr, uint32_t cap = 0, uint32_t *zero_classes = nullptr,
-                       uint32_t *fctl = nullptr, void *bin_base = nullptr, uint32_t seg_len = 0, uint32_t fseg_len = 0,
-                       uint32_t *host_tilelist = nullptr, uint32_t *fwd_ready = nullptr, uint32_t fseg_min = 0);
+void launch_tile_order(const uint2 *ranges, int T, int shift, uint32_t *order, hipStream_t s, const uint32_t *kdev,
+                       uint32_t cap, uint32_t *zero_classes, uint32_t *fctl, void *bin_base, uint32_t seg_len,
+                       uint32_t fseg_len, uint32_t *host_tilelist, uint32_t *fwd_ready, uint32_t fseg_min);
 void launch_mark_visible(int P, const float *means3D, const float *view, uint8_t *present, hipStream_t s);
 
 // sort.hip (rocPRIM)
@@ -109,9 +109,6 @@ uint32_t *dsort_aux_word(const GeomState &gs);
 uint32_t *dsort_maxsb_word(const GeomState &gs);
 // the forward split's queue-ready word (zeroed with the control words by every frame's preprocess)
 uint32_t *dsort_fwdready_word(const GeomState &gs);
-// the frame's longest tile list and superblock list, [2] (zeroed by the preprocess; render_fwd copies
-// them to the pinned host words)
-uint32_t *dsort_longest_words(const GeomState &gs);
 int device_cus();  // compute units of the current device (rasterizer.hip, cached)
 uint32_t *dsort_live_words(const GeomState &gs);
 uint32_t *dsort_culled_word(const GeomState &gs);  // culled Gaussians of the frame (the upsweep's sum)
@@ -125,10 +122,7 @@ int sort_cap();  // the longest SB list the local sort holds
 int debug_trace(int64_t *out, int n, int reset);  // GSR_SB_TRACE builds: sb_sort_bin phase stamps
 // level-1 counts and SB bases; with fw.dev_K set (local sort) the column scan also stores K, the
 // longest SB list and the level-1 total (FrameWords)
-// sb_order != NULL: the SBs in forward launch order (GSR_FWD_SB_ORDER); zero_classes != NULL: the
-// backward class counters render_fwd fills are zeroed (GSR_BWD_CLS)
 void launch_binning_count(int P, const Camera &cam, const GeomState &gs, bool index_order, const FrameWords &fw,
-                          uint32_t *sb_order, uint32_t *zero_classes,
                           hipStream_t s, uint32_t tb_split = 0, uint32_t *host_sblist = nullptr);
 void launch_binning_scatter(int P, const Camera &cam, const GeomState &gs, const BinningState &bs, bool index_order,
                             hipStream_t s);
@@ -154,11 +148,9 @@ struct ZeroRows {
 
 // render.hip
 void launch_render_fwd(const Camera &cam, const GeomState &gs, const BinningState &bs, const ImageState &is,
-                       const float *bg, float *out_color, float *out_invdepth, hipStream_t s, bool need_bwd = true,
-                       bool sb_order = false, uint32_t seg_len = 0, uint32_t fseg_len = 0,
-                       hipStream_t worker_stream = nullptr, bool workers_launched = false,
-                       const uint32_t *longest = nullptr, uint32_t *host_words = nullptr, uint32_t fseg_min = 0,
-                       FwdSpin spin = FwdSpin{kFwdReadySpins, kFwdFlagSpins, nullptr});
+                       const float *bg, float *out_color, float *out_invdepth, hipStream_t s, bool need_bwd,
+                       uint32_t seg_len, uint32_t fseg_len, hipStream_t worker_stream, bool workers_launched,
+                       uint32_t fseg_min, FwdSpin spin);
 // Forward segments' worker pool launched ahead of tile_order (on a side stream that has waited for
 // the binning and the colour pass): its workgroups are resident before render_fwd's grid fills the
 // CUs and start on the queue as soon as tile_order (given the same word) releases `ready`
@@ -182,7 +174,6 @@ void launch_render_bwd(const Camera &cam, const GeomState &gs, const BinningStat
                        const BwdScratch &sc, hipStream_t s, const ZeroRows *zr = nullptr, uint32_t seg_len = 0);
 bool bwd_segments_supported();
 bool fwd_segments_supported();
-bool fwd_segments_in_kernel();  // the worker pool inside render_fwd's launch (no side stream)
 uint32_t fseg_min_len(uint32_t Lf);  // the shortest list the forward split takes
 uint32_t set_fwd_split_min(uint32_t len);  // gsr_set_fwd_split_min
 
@@ -224,8 +215,7 @@ void launch_preprocess_bwd(const GaussianInputs &in, const Camera &cam, const Ge
                            const int *radii, const BwdScratch &sc, const GaussianGrads &out, hipStream_t s,
                            const ZeroRows *zr = nullptr);
 // the frame's gradient arrays for render_bwd to zero and its live stamps (false: preprocess_bwd
-// writes the zeros itself -- record mode, the single-kernel path, unaligned arrays or
-// GSR_BWD_ZERO_IN_RENDER=0)
+// writes the zeros itself -- record mode, the single-kernel path or unaligned arrays)
 bool bwd_zero_rows(const GaussianInputs &in, const GaussianGrads &out, const BwdScratch &sc, uint32_t *gs_stamps,
                    int nblocks, ZeroRows *z);
 

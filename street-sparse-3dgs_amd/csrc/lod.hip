@@ -20,12 +20,14 @@
 // (oracle/gs_oracle.c gso_expand_to_size / gso_interpolation_weights), not to the unvendored
 // extension ("parity unpinned" against gaussianhierarchy itself).
 //
-// MI355X mapping: expand_to_size is one launch (lod_cut_kernel): a workgroup per 1024 nodes stages
-// the nodes through LDS (4 KiB per load instruction), reads each node's box (and its parent's box
-// and first Gaussian where the decision needs them; parents of consecutive nodes are consecutive in
-// a level-ordered hierarchy, so they stay in L2), scans the counts, takes its offset by a
-// decoupled lookback over the preceding tiles and writes (render index, parent's first Gaussian,
-// node) per rendered Gaussian.  The host reads the total once (the value expand_to_size returns).
+// MI355X mapping: expand_to_size is a count launch and a write launch over tiles of 1024 nodes, with
+// a one-workgroup scan of the group sums between them for large hierarchies (the kernels' comment
+// below).  The count launch reads each node's box (and its parent's box and first Gaussian where the
+// decision needs them; parents of consecutive nodes are consecutive in a level-ordered hierarchy, so
+// they stay in L2), scans the tile's counts and leaves a record per rendered node and the tile's sum
+// (added to its group's); the write launch forms each tile's offset from the group and tile sums --
+// no workgroup waits for another -- and writes (render index, parent's first Gaussian, node) per
+// rendered Gaussian.  The host reads the total once (the value expand_to_size returns).
 #include <algorithm>
 #include <cfloat>
 #include <cstring>
@@ -370,7 +372,8 @@ int gsr_expand_to_size(int64_t N, const int *nodes, const float *boxes, float ta
     const int64_t ntiles = (N + kCutTile - 1) / kCutTile;
     CutScratch sc;
     (void)cut_scratch_bytes(ntiles, &sc, reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(scratch), 256)));
-    // the done counter, the total and the group sums
+    // the control words (the total the write launch's last tile stores) and the group sums the count
+    // launch's tiles add into
     hipError_t e = hipMemsetAsync(sc.ctl, 0, sizeof(uint64_t) * (size_t)(kCutHead + cut_groups(ntiles)), s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(lod_cut_count_kernel, dim3((unsigned)ntiles), dim3(kCutThreads), 0, s, N, ntiles, nodes,

@@ -63,18 +63,14 @@ thread_local gsr::StepAct g_step_act{};    // set_step_act
 std::atomic<int> g_live_list{0};           // gsr_set_live_list
 thread_local bool g_step_act_done = false;
 constexpr int kMaxDevicesK = 64;
-// The backward's per-Gaussian accumulator rows (64 B each: render_bwd's ten float-atomic sums),
-// GSR_PERSISTENT_ACC (default): one grow-only array per device, all zero between backwards --
+// The backward's per-Gaussian accumulator rows (64 B each: render_bwd's ten float-atomic sums):
+// one grow-only array per device, all zero between backwards --
 // render_bwd adds into the rows of the Gaussians it reaches and the consumer (preprocess_bwd or
 // the live-row pass) zeroes every row it reads (it always did, for a repeated backward), so the
 // forward no longer clears P rows per frame (1M x 64 B on the bench frame: 10 us of the step,
 // r06r).  A backward that fails between render_bwd and the consumer leaves the rows marked dirty
 // (cleared by the next backward); a backward on another stream than the previous one first waits
-// for that stream.  GSR_PERSISTENT_ACC=0: the rows in the frame's geometry buffer, cleared by
-// render_fwd (rounds 1-5).
-#ifndef GSR_PERSISTENT_ACC
-#define GSR_PERSISTENT_ACC 1
-#endif
+// for that stream.
 struct AccRows {
     float4 *p = nullptr;
     size_t rows = 0;
@@ -126,9 +122,6 @@ constexpr int kKHist = 256;
 thread_local int64_t g_khint[kMaxDevicesK] = {};
 thread_local int64_t g_khist[kMaxDevicesK][kKHist] = {};
 thread_local int g_khead[kMaxDevicesK] = {};
-#ifndef GSR_DEFER_K
-#define GSR_DEFER_K 1
-#endif
 constexpr uint32_t kKPending = 0xFFFFFFFFu;
 // The split gate (gsr_set_split_gate): the forward split and the tile_bin split cost launches and
 // stream hand-offs on every frame they are armed for, and pay only on frames with very long lists
@@ -158,16 +151,7 @@ constexpr int kSides = 2;  // 0: the colour pass and the forward segments' worke
 hipStream_t g_side[kSides][kMaxDevices] = {};
 hipEvent_t g_fork[kSides][kMaxDevices] = {}, g_join[kSides][kMaxDevices] = {};
 
-#ifndef GSR_SIDE_STREAM
-#define GSR_SIDE_STREAM 1
-#endif
-#ifndef GSR_COLOR_SERIAL
-#define GSR_COLOR_SERIAL 0  // 1: SH colour pass on the main stream after the preprocess (measured: no faster)
-#endif
-#ifndef GSR_K_POLL
-#define GSR_K_POLL 1  // deferred K read by polling the pinned word (0: an event after the upsweep)
-#endif
-bool side_stream(hipStream_t main, hipStream_t *side, hipEvent_t *fork, hipEvent_t *join, int which = 0) {
+bool side_stream(hipStream_t *side, hipEvent_t *fork, hipEvent_t *join, int which = 0) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
     std::lock_guard<std::mutex> lk(g_side_mu);
@@ -177,7 +161,7 @@ bool side_stream(hipStream_t main, hipStream_t *side, hipEvent_t *fork, hipEvent
             hipEventCreateWithFlags(&g_join[which][dev], hipEventDisableTiming) != hipSuccess)
             return false;
     }
-    *side = GSR_SIDE_STREAM ? g_side[which][dev] : main;  // 0: the colour pass serialises (timing experiments)
+    *side = g_side[which][dev];
     *fork = g_fork[which][dev];
     *join = g_join[which][dev];
     return true;
@@ -320,16 +304,12 @@ GeomState carve_geom(void *base, int P, int gx, int gy, size_t *bytes) {
     g.drect = c.take<uint2>(P);
     g.rect8 = c.take<uint2>(P);
     g.rect4 = c.take<uint32_t>(P);
-    if (!GSR_RECT4 || gx > 255 || gy > 255) g.rect4 = nullptr;
+    if (gx > 255 || gy > 255) g.rect4 = nullptr;
     g.sb = sb_grid(gx, gy, P);
     g.sb_cnt_g = c.take<uint32_t>((size_t)g.sb.nsb * g.sb.ccols);
     g.sb_cnt_i = c.take<uint32_t>((size_t)g.sb.nsb * g.sb.ccols);
     g.sb_base_g = c.take<uint32_t>((size_t)g.sb.nsb + 1);
     g.sb_base_i = c.take<uint32_t>((size_t)g.sb.nsb + 1);
-    // GSR_PERSISTENT_ACC: the backward's accumulator rows are the device's persistent rows
-    // (acc_rows below), not part of the frame's buffer
-    g.acc = GSR_PERSISTENT_ACC ? nullptr : c.take<float4>(4 * (size_t)P);
-    g.nacc = GSR_PERSISTENT_ACC ? 0 : P;
     g.live_stamp = c.take<uint32_t>(P);
     g.tb_flag = c.take<uint32_t>((size_t)g.sb.nsb + 1);
     g.tb_items = c.take<uint32_t>(kTBMaxItems);
@@ -381,14 +361,13 @@ ImageState carve_image(void *base, int T, int npix, size_t *bytes) {
     s.n_contrib = c.take<uint32_t>(npix);
     s.tile_work = c.take<uint32_t>(T);
     s.tile_ids = c.take<uint32_t>(T);
-    s.tile_order = c.take<uint32_t>(T);
     s.bwd_cnt = c.take<uint32_t>(kBwdClasses + 64);  // + the segment count (kBwdSegCount)
     s.bwd_cls = c.take<uint32_t>((size_t)kBwdClasses * T);
     if (bytes) *bytes = align_up(c.off, 256);
     return s;
 }
 
-// atomic mode needs no scratch (the accumulators live in the geometry buffer, GeomState.acc)
+// atomic mode needs no record scratch (the accumulators are the device's persistent rows, acc_rows)
 BwdScratch carve_bwd(void *base, int64_t K, int P, bool atomic, size_t *bytes, bool list) {
     Carver c(base);
     BwdScratch s{};
@@ -514,7 +493,8 @@ void gsr::note_step_act_done(bool done) { g_step_act_done = done; }
 bool gsr::step_act_done() { return g_step_act_done; }
 
 namespace {
-// Geometry buffers whose accumulator rows the forward did not clear: forwards made with
+// Geometry buffers of forwards no atomic-mode backward may follow ("uncleared": until round 6 the
+// forward cleared per-frame accumulator rows for the others): forwards made with
 // GSR_FWD_NO_BACKWARD (a backward handed one fails loudly) and forwards made in deterministic
 // mode (their backward uses the record path even if the mode was switched in between).  Every
 // forward first removes its own buffer, so an address the caching allocator hands out again is
@@ -639,8 +619,9 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
     HostScope host_scope(10);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (flags & ~(unsigned)GSR_FWD_NO_BACKWARD) return fail(GSR_ERR_INVALID_ARGUMENT, "unknown forward flags");
-    // the backward's accumulator rows are cleared (and its launch order built) only for a frame a
-    // backward may follow: atomic mode, GSR_FWD_NO_BACKWARD not set
+    // the backward's launch order (render_fwd's work classes) is built only for a frame a backward
+    // may follow (GSR_FWD_NO_BACKWARD not set); clear_acc: such a frame in atomic mode, whose backward
+    // adds into the device's accumulator rows (they are all zero between backwards, acc_rows)
     const bool need_bwd = !(flags & GSR_FWD_NO_BACKWARD);
     const bool det_fwd = g_deterministic.load(std::memory_order_relaxed) != 0;
     const bool clear_acc = need_bwd && !det_fwd;
@@ -667,12 +648,9 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
     // place, no R-row copy written and re-read) for frames no backward follows (render_hierarchy.py's
     // no_grad frames); a frame a backward may follow keeps the blended rows in its geometry buffer,
     // where the backward reads them
-#ifndef GSR_CUT_FUSED
-#define GSR_CUT_FUSED 1
-#endif
     GaussianInputs probe{P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                          scale_modifier, g_raw_params ? 1 : 0};
-    const bool fuse_cut = GSR_CUT_FUSED && R > 0 && !need_bwd && cut_fusable(probe);
+    const bool fuse_cut = R > 0 && !need_bwd && cut_fusable(probe);
 
     const Camera cam = make_camera(viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, width, height);
     const int T = cam.gx * cam.gy;
@@ -686,8 +664,7 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
     void *gbase = geom_buffer(resize_ctx, gbytes);
     void *ibase = image_buffer(resize_ctx, ibytes);
     if (!gbase || !ibase) return fail(GSR_ERR_ALLOCATION, "geometry/image buffer allocation failed");
-    GeomState gs = carve_geom(gbase, P, cam.gx, cam.gy, nullptr);
-    if (!clear_acc) gs.nacc = 0;
+    const GeomState gs = carve_geom(gbase, P, cam.gx, cam.gy, nullptr);
     note_forward_geom(gbase, need_bwd, clear_acc);
     const ImageState is = carve_image(ibase, T, npix, nullptr);
     if (R > 0 && !fuse_cut) {
@@ -711,17 +688,10 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
     if (fuse_cut) in.cut = CutRef{render_indices, parent_indices, interpolation_weights, Nin};
     hipStream_t side = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
-    // GSR_COLOR_SERIAL=1 runs the SH colour pass on the main stream right after the preprocess:
-    // beside the binning on the side stream it slows the binning by about its own length (both
-    // want the CUs), but run serially it costs the same (2490-2498 vs 2540 Mpix/s), so the side
-    // stream stays the default.
-    const bool split = P > 0 && color_split_supported(in) &&
-                       (GSR_COLOR_SERIAL || side_stream(s, &side, &fork, &join));
+    // the SH colour pass runs on the side stream, beside the sort and / or the binning
+    const bool split = P > 0 && color_split_supported(in) && side_stream(&side, &fork, &join);
     if (fuse_cut && !split) return fail(GSR_ERR_DEVICE, "hierarchy cut: the fused blend needs the SH colour pass");
     SideJoin sj;
-#ifndef GSR_COLOR_FORK
-#define GSR_COLOR_FORK 2  // 0: beside the sort and the binning; 1: beside the binning only; 2: chosen per frame
-#endif
 #ifndef GSR_COLOR_LOCAL_BLOCKS
 #define GSR_COLOR_LOCAL_BLOCKS 128  // local-sort frames: the colour pass's persistent grid beside the binning
 #endif
@@ -737,28 +707,26 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
     // binning, at full width.  Local-sort frames fork it right after the preprocess too, as a
     // persistent grid of GSR_COLOR_LOCAL_BLOCKS blocks beside the binning.
     int color_blocks = 0;
-    bool color_early = GSR_COLOR_FORK == 0;
-    if (local && split && !GSR_COLOR_SERIAL) {
-        color_early = GSR_COLOR_FORK != 1;  // 1: after the level-1 counts, beside the scatter and the sort
+    bool color_early = false;
+    if (local && split) {
+        color_early = true;
         color_blocks = GSR_COLOR_LOCAL_BLOCKS;
-    } else if (GSR_COLOR_FORK == 2 && split && !GSR_COLOR_SERIAL) {
-        {
-            // workgroups are dealt round-robin over the 8 XCDs: leave every XCD room for its share
-            // of the sort's workgroups (123 of them -> 16 per XCD -> 8 x (32 - 16) = 128 colour blocks)
-            const int per_xcd = device_cus() / 8;
-            const int free_cus = 8 * (per_xcd - (dsort_blocks(P) + 7) / 8);
-            if (free_cus >= 2 * per_xcd) {
-                color_early = true;
-                color_blocks = free_cus;
-            } else {
-                // the sort fills the chip (large P).  Two rounds of it or more (config 5's 7.46M rows):
-                // the colour pass forks right after the preprocess, so it overlaps the sort as well
-                // as the binning (config 5 3.62 -> 3.51 ms, r05f); config 3's 3M-row frames measured
-                // no gain (55.0 vs 55.3 s), so they keep the fork after the sort.  Either way a full
-                // grid of 8-wave blocks.
-                color_early = dsort_blocks(P) >= 2 * device_cus();
-                color_blocks = 0;
-            }
+    } else if (split) {
+        // workgroups are dealt round-robin over the 8 XCDs: leave every XCD room for its share
+        // of the sort's workgroups (123 of them -> 16 per XCD -> 8 x (32 - 16) = 128 colour blocks)
+        const int per_xcd = device_cus() / 8;
+        const int free_cus = 8 * (per_xcd - (dsort_blocks(P) + 7) / 8);
+        if (free_cus >= 2 * per_xcd) {
+            color_early = true;
+            color_blocks = free_cus;
+        } else {
+            // the sort fills the chip (large P).  Two rounds of it or more (config 5's 7.46M rows):
+            // the colour pass forks right after the preprocess, so it overlaps the sort as well
+            // as the binning (config 5 3.62 -> 3.51 ms, r05f); config 3's 3M-row frames measured
+            // no gain (55.0 vs 55.3 s), so they keep the fork after the sort.  Either way a full
+            // grid of 8-wave blocks.
+            color_early = dsort_blocks(P) >= 2 * device_cus();
+            color_blocks = 0;
         }
     }
     auto fork_color = [&](const int *vis_radii) -> int {
@@ -775,29 +743,19 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
         sj.pending = true;
         return check("preprocess colour", debug, side);
     };
-#ifndef GSR_COLOR_PRE_CUT
-#define GSR_COLOR_PRE_CUT 1
-#endif
     // A fused hierarchy cut whose colour pass forks early (config 5): forked before the preprocess,
     // so it overlaps the preprocess as well; it then colours every row (no radii yet: a cut frame's
     // rows are all in view) and writes only the colour quarter of each render record and the clamp
     // bits, which the preprocess leaves to it.  Config 5's raster part 2.30 -> 2.28 ms (r06zt,
     // interleaved; the pass itself 1.44 -> 1.85 ms, longer but off the critical path).
-    const bool pre_fork = GSR_COLOR_PRE_CUT && fuse_cut && split && !GSR_COLOR_SERIAL && color_early;
+    const bool pre_fork = fuse_cut && split && color_early;
     if (pre_fork && (rc = fork_color(nullptr))) return rc;
     {
         StageTimer st(0, s);
         launch_preprocess(in, cam, gs, radii, s, split);
     }
     if ((rc = check("preprocess", debug, s))) return rc;
-    if (split && GSR_COLOR_SERIAL) {
-        {
-            StageTimer st(8, s);
-            launch_preprocess_color(in, cam, gs, radii, s);
-        }
-        if ((rc = check("preprocess colour", debug, s))) return rc;
-    }
-    if (split && !GSR_COLOR_SERIAL && color_early && !pre_fork && (rc = fork_color(radii))) return rc;
+    if (split && color_early && !pre_fork && (rc = fork_color(radii))) return rc;
     // K sizes the point list.  With a capacity hint from this device's previous frame the binning
     // and the forward render are queued first and K is read afterwards (the GPU never waits on
     // the host's hand-off); kernels that would overrun the capacity exit at once (they compare the
@@ -806,7 +764,7 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesK)
         return fail(GSR_ERR_DEVICE, "no current device");
-    const bool defer = GSR_DEFER_K && P > 0 && !debug && g_khint[dev] > 0;
+    const bool defer = P > 0 && !debug && g_khint[dev] > 0;
     hipEvent_t k_ready = nullptr;
     if (P > 0) {
         if (!g_pinned) {
@@ -821,21 +779,16 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
             return fail(GSR_ERR_DEVICE, "event creation failed");
         // deferred K: no event -- its marker packet cost a ~7 us gap before the first sort pass;
         // the host polls the pinned word the upsweep / column scan stores instead (read_K)
-        k_ready = (defer && GSR_K_POLL) ? nullptr : g_k_ready[dev];
+        k_ready = defer ? nullptr : g_k_ready[dev];
         __atomic_store_n(&g_pinned[kHostWide], 0u, __ATOMIC_RELAXED);
         __atomic_store_n(&g_pinned[kHostK], kKPending, __ATOMIC_SEQ_CST);
     }
     const FrameWords fw_local{dsort_K_word(gs), dsort_maxsb_word(gs), g_pinned_dev};
     const FrameWords fw_none{nullptr, nullptr, nullptr};
-    // the forward's launch order by superblock and the backward class counters zeroed, both by the
-    // level-1 column scan (no tile_order launch); P == 0 frames run no binning: tile_order does both
-    const bool sb_order = GSR_FWD_SB_ORDER && P > 0;
-    uint32_t *const order_sb = sb_order ? is.tile_ids : nullptr;
-    uint32_t *const zero_cls = GSR_BWD_CLS && need_bwd && sb_order ? is.bwd_cnt : nullptr;
     if (local) {
         {
             StageTimer st(1, s);  // level-1 counts, SB bases, K
-            launch_binning_count(P, cam, gs, true, fw_local, order_sb, zero_cls, s, false);
+            launch_binning_count(P, cam, gs, true, fw_local, s);
             if (k_ready) (void)hipEventRecord(k_ready, s);
         }
         if ((rc = check("binning (counts)", debug, s))) return rc;
@@ -909,10 +862,10 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
         if ((rc = read_K())) return rc;
         if (local && maxsb > (uint32_t)sort_cap() && (rc = to_global())) return rc;
     }
-    if (split && !GSR_COLOR_SERIAL && !color_early && (rc = fork_color(radii))) return rc;
+    if (split && !color_early && (rc = fork_color(radii))) return rc;
     bool joined = false;
     const uint32_t seg_req = need_bwd && bwd_segments_supported() ? g_bwd_seg.load(std::memory_order_relaxed) : 0u;
-    uint32_t fseg_req = fwd_segments_supported() && !sb_order ? g_fwd_seg.load(std::memory_order_relaxed) : 0u;
+    uint32_t fseg_req = fwd_segments_supported() ? g_fwd_seg.load(std::memory_order_relaxed) : 0u;
     uint32_t tb_req = GSR_TB_SPLIT;  // the list length past which tile_bin slices a superblock (0: off)
     // the split's minimum list length, read once per frame: tile_order's queue, render_fwd's skip test
     // and the gate must agree even if gsr_set_fwd_split_min runs meanwhile
@@ -951,9 +904,7 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
         {
             StageTimer st(2, s);
             if (!local && !counted)
-                launch_binning_count(P, cam, gs, false, fw_none, order_sb, zero_cls, s, tbs,
-                                     GSR_HOST_WORDS == 2 ? dsort_longest_words(gs) + 1
-                                     : GSR_HOST_WORDS ? g_pinned_dev + kHostSBList : nullptr);
+                launch_binning_count(P, cam, gs, false, fw_none, s, tbs, g_pinned_dev + kHostSBList);
             launch_binning_scatter(P, cam, gs, bs, local, s);
         }
         if ((r = check("binning (superblocks)", debug, s))) return r;
@@ -963,7 +914,7 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
             // still carry the colour pass)
             hipStream_t ts = s;
             hipEvent_t tf = nullptr, tj = nullptr;
-            const bool tfork = tbs != 0u && side_stream(s, &ts, &tf, &tj, 1) && ts != s;
+            const bool tfork = tbs != 0u && side_stream(&ts, &tf, &tj, 1);
             if (tfork && (hipEventRecord(tf, s) != hipSuccess || hipStreamWaitEvent(ts, tf, 0) != hipSuccess))
                 return fail(GSR_ERR_DEVICE, "side stream fork failed");
             launch_binning_tiles(P, cam, gs, bs, is, local, dsort_maxsb_word(gs), s, tbs != 0u, tfork ? ts : nullptr);
@@ -977,28 +928,25 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
         hipStream_t ws = s;
         hipEvent_t wf = nullptr, wj = nullptr;
         bool early = false;
-        if (fseg_used && !sb_order && g_fwd_early_workers.load(std::memory_order_relaxed) &&
-            !fwd_segments_in_kernel() && side_stream(s, &ws, &wf, &wj, 1) && ws != s) {
+        if (fseg_used && g_fwd_early_workers.load(std::memory_order_relaxed) && side_stream(&ws, &wf, &wj, 1)) {
             if (hipEventRecord(wf, s) != hipSuccess || hipStreamWaitEvent(ws, wf, 0) != hipSuccess ||
-                (split && !GSR_COLOR_SERIAL && !joined && hipStreamWaitEvent(ws, join, 0) != hipSuccess))
+                (split && !joined && hipStreamWaitEvent(ws, join, 0) != hipSuccess))
                 return fail(GSR_ERR_DEVICE, "side stream fork failed");
             launch_render_fwd_workers(cam, gs, bs, is, background, out_color, out_invdepth, need_bwd, seg_used,
                                       fseg_used, ws, dsort_fwdready_word(gs), spin);
             if (hipEventRecord(wj, ws) != hipSuccess) return fail(GSR_ERR_DEVICE, "side stream join record failed");
             early = true;
         }
-        if (!sb_order) {
+        {
             StageTimer st(4, s);
             // forward order: by list length (and the backward's class counters zeroed)
-            launch_tile_order(nullptr, is.ranges, T, 4, is.tile_ids, s, bs.kdev, bs.cap,
-                              GSR_BWD_CLS && need_bwd ? is.bwd_cnt : nullptr, is.bwd_cnt + kFwdItemsWord, bs.point_list,
-                              seg_used, fseg_used,
-                              P > 0 && GSR_HOST_WORDS == 2 ? dsort_longest_words(gs)
-                              : P > 0 && GSR_HOST_WORDS ? g_pinned_dev + kHostTileList : nullptr,
+            launch_tile_order(is.ranges, T, 4, is.tile_ids, s, bs.kdev, bs.cap,
+                              need_bwd ? is.bwd_cnt : nullptr, is.bwd_cnt + kFwdItemsWord, bs.point_list, seg_used,
+                              fseg_used, P > 0 ? g_pinned_dev + kHostTileList : nullptr,
                               early ? dsort_fwdready_word(gs) : nullptr, fseg_min);
         }
         if ((r = check("tile order", debug, s))) return r;
-        if (split && !GSR_COLOR_SERIAL && !joined) {
+        if (split && !joined) {
             sj.pending = false;
             joined = true;
             if (hipStreamWaitEvent(s, join, 0) != hipSuccess) return fail(GSR_ERR_DEVICE, "side stream join failed");
@@ -1009,13 +957,12 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
             // split tiles); joined before anything reads the frame
             hipStream_t wside = s;
             hipEvent_t wfork = nullptr, wjoin = nullptr;
-            if (fseg_used && !early && !fwd_segments_in_kernel() && !side_stream(s, &wside, &wfork, &wjoin)) wside = s;
+            if (fseg_used && !early && !side_stream(&wside, &wfork, &wjoin)) wside = s;
             const bool forked = fseg_used && !early && wside != s;
             if (forked && (hipEventRecord(wfork, s) != hipSuccess || hipStreamWaitEvent(wside, wfork, 0) != hipSuccess))
                 return fail(GSR_ERR_DEVICE, "side stream fork failed");
-            launch_render_fwd(cam, gs, bs, is, background, out_color, out_invdepth, s, need_bwd, sb_order, seg_used,
-                              fseg_used, wside, early, P > 0 && GSR_HOST_WORDS == 2 ? dsort_longest_words(gs) : nullptr,
-                              g_pinned_dev, fseg_min, spin);
+            launch_render_fwd(cam, gs, bs, is, background, out_color, out_invdepth, s, need_bwd, seg_used, fseg_used,
+                              wside, early, fseg_min, spin);
             // the early pool's workers may have given up on the ready word (the two streams did not
             // run concurrently): a small second launch on this stream, after tile_order, takes any
             // item still queued -- no frame depends on the streams' concurrency
@@ -1025,10 +972,6 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
             if (forked && (hipEventRecord(wjoin, wside) != hipSuccess || hipStreamWaitEvent(s, wjoin, 0) != hipSuccess))
                 return fail(GSR_ERR_DEVICE, "side stream join failed");
             if (early && hipStreamWaitEvent(s, wj, 0) != hipSuccess) return fail(GSR_ERR_DEVICE, "side stream join failed");
-        }
-        if (need_bwd && !GSR_BWD_CLS) {
-            StageTimer st(9, s);  // backward launch order, from the forward's per-tile work
-            launch_tile_order(is.tile_work, is.ranges, T, 2, is.tile_order, s, bs.kdev, bs.cap);
         }
         return check("render", debug, s);
     };
@@ -1138,8 +1081,7 @@ int gsr_rasterize_backward(gsr_resize_fn scratch, void *resize_ctx, int P, int D
     void *sbase = scratch(resize_ctx, std::max<size_t>(sbytes, 256));  // atomic mode: the live masks only
     if (!sbase) return fail(GSR_ERR_ALLOCATION, "backward scratch allocation failed");
     BwdScratch sc = carve_bwd(sbase, R_inst, P, atomic, nullptr, list);
-    sc.acc = gs.acc;
-    if (GSR_PERSISTENT_ACC && atomic && P > 0 && !(sc.acc = acc_rows(s, (size_t)P)))
+    if (atomic && P > 0 && !(sc.acc = acc_rows(s, (size_t)P)))
         return fail(GSR_ERR_ALLOCATION, "backward accumulator rows allocation failed");
 
     // sparse rows only for plain frames (the cut's rows are scattered to the input rows below)
@@ -1186,7 +1128,7 @@ int gsr_rasterize_backward(gsr_resize_fn scratch, void *resize_ctx, int P, int D
         StageTimer st(7, s);
         launch_preprocess_bwd(in, cam, gs, is, radii, sc, out, s, zeroed ? &zr : nullptr);
     }
-    if (GSR_PERSISTENT_ACC && atomic && P > 0) acc_rows_consumed();  // the consumer zeroes what it reads
+    if (atomic && P > 0) acc_rows_consumed();  // the consumer zeroes what it reads
     if ((rc = check("preprocess backward", debug, s))) return rc;
     if (R > 0) {
         const size_t n3 = sizeof(float) * 3 * (size_t)Nin;

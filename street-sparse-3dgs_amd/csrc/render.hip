@@ -68,10 +68,6 @@ struct StatAcc {
     }
 };
 
-#ifndef GSR_EXACT_CULL
-#define GSR_EXACT_CULL 3  // bit 0: forward, bit 1: backward
-#endif
-
 __device__ __forceinline__ uint32_t sub_block_mask(const float4 &qa, const float4 &qb, float tm, float tx0,
                                                    float ty0) {
     // bit k: the alpha >= 1/255 ellipse of the instance (its box, then the ellipse itself) meets
@@ -83,7 +79,7 @@ __device__ __forceinline__ uint32_t sub_block_mask(const float4 &qa, const float
     for (int k = 0; k < kPixPerLane; k++) {
         const float y0 = ty0 + (float)(4 * k);
         if (Y + ey >= y0 && Y - ey <= y0 + 3.f &&
-            (!(GSR_EXACT_CULL & 2) || ellipse_meets_box(X, Y, qa.z, qa.w, qb.x, tm, tx0, tx0 + 15.f, y0, y0 + 3.f)))
+            ellipse_meets_box(X, Y, qa.z, qa.w, qb.x, tm, tx0, tx0 + 15.f, y0, y0 + 3.f))
             m |= 1u << k;
     }
     return m;
@@ -104,12 +100,6 @@ __device__ __forceinline__ uint32_t lane_prefix(uint64_t mask) {
 // The gather is software-pipelined: while batch b blends, the GRec lines of batch b+1 and the
 // point-list ids of batch b+2 are in flight (two dependent round trips per batch -- id, then the
 // line -- that were otherwise exposed once per batch per wave).
-#ifndef GSR_ACC_NT
-#define GSR_ACC_NT 1
-#endif
-#ifndef GSR_FWD_ACC_CLEAR
-#define GSR_FWD_ACC_CLEAR 1  // 0: measurement builds only (the backward's sums then start from garbage)
-#endif
 #ifndef GSR_FWD_SUB
 #define GSR_FWD_SUB 1  // 16x4 sub-blocks per wave (measured: 1 -> 0.139 ms, 2 -> 0.176, 4 -> 0.242)
 #endif
@@ -137,19 +127,9 @@ __device__ __forceinline__ void fwd_gather(const GRec *__restrict__ rec, uint32_
 // serial per wave.  The wave's walk stops when all its pixels have saturated; saturated
 // sub-blocks drop out of the cull mask at the next batch and an instance's culled sub-blocks are
 // skipped with scalar branches.  The list position comes from LDS with the instance (no scalar
-// bit scan and no SGPR->VGPR move per pixel).  Per-pixel arithmetic in the oracle's order.
-// GSR_FWD_POLY=1 evaluates the exponent as a quadratic in the pixel's offset from its sub-block's
-// centre (5 FMAs; ~3 us faster on the bench frame) -- off: its p2 differs from the backward's
-// replay (and the oracle's) by up to 3e-5, and the backward reconstructs T from final_T by
-// dividing out (1 - alpha) of every instance, so the forward and the replay must agree on alpha
-// bit for bit.  With the quadratic, near Gaussians clamped at alpha = 0.99 amplified the mismatch
-// into 1e-3 relative gradient errors (1536x1536 street frame, SH degree 1: means3D 3.5e-4 rel L2).
-#ifndef GSR_FWD_POLY
-#define GSR_FWD_POLY 0
-#endif
-#ifndef GSR_FWD_MASKSEL
-#define GSR_FWD_MASKSEL 1
-#endif
+// bit scan and no SGPR->VGPR move per pixel).  Per-pixel arithmetic in the oracle's order: the
+// backward reconstructs T from final_T by dividing out (1 - alpha) of every instance, so the
+// forward and the replay must agree on alpha bit for bit.
 constexpr int kFcmpUGE = 11, kFcmpULE = 13;  // llvm::CmpInst unordered-or predicates: !(x < y), !(x > y)
 // per-lane select by a wave mask held in SGPRs (mask bit set: t)
 __device__ __forceinline__ float lane_select(uint64_t mask, float t, float f) {
@@ -158,9 +138,6 @@ __device__ __forceinline__ float lane_select(uint64_t mask, float t, float f) {
     return r;
 }
 
-#ifndef GSR_FWD_EARLY_EXIT
-#define GSR_FWD_EARLY_EXIT 1  // leave a batch once every pixel of the sub-block has saturated
-#endif
 template <int kSub>
 __device__ __forceinline__ uint32_t sub_block_mask_n(const float4 &qa, const float4 &qb, float tm, float tx0,
                                                      float ty0) {
@@ -171,7 +148,7 @@ __device__ __forceinline__ uint32_t sub_block_mask_n(const float4 &qa, const flo
     for (int k = 0; k < kSub; k++) {
         const float y0 = ty0 + (float)(4 * k);
         if (Y + ey >= y0 && Y - ey <= y0 + 3.f &&
-            (!(GSR_EXACT_CULL & 1) || ellipse_meets_box(X, Y, qa.z, qa.w, qb.x, tm, tx0, tx0 + 15.f, y0, y0 + 3.f)))
+            ellipse_meets_box(X, Y, qa.z, qa.w, qb.x, tm, tx0, tx0 + 15.f, y0, y0 + 3.f))
             m |= 1u << k;
     }
     return m;
@@ -536,97 +513,30 @@ __global__ __launch_bounds__(kWave * kPixPerLane) void render_fwd_seg_kernel(
     }
 }
 
-#ifndef GSR_FWD_SEG_INKERNEL
-#define GSR_FWD_SEG_INKERNEL 0  // 1: the worker pool as render_fwd's first workgroups (no side stream)
-#endif
-#if GSR_FWD_SEG_INKERNEL
-#define GSR_FWD_ATTR __attribute__((amdgpu_waves_per_eu(8)))
-#else
-#define GSR_FWD_ATTR
-#endif
 template <int kSub>
-__global__ __launch_bounds__(kWave * (kPixPerLane / kSub)) GSR_FWD_ATTR void render_fwd_kernel(
+__global__ __launch_bounds__(kWave * (kPixPerLane / kSub)) void render_fwd_kernel(
     const uint2 *__restrict__ ranges, const uint32_t *__restrict__ point_list, int W, int H, int gx,
     const GRec *__restrict__ rec, const float *__restrict__ bg, float *__restrict__ out_color,
     float *__restrict__ out_invd, float *__restrict__ final_T, uint32_t *__restrict__ n_contrib,
     uint32_t *__restrict__ tile_work, const uint32_t *__restrict__ fwd_order, const uint32_t *__restrict__ kdev,
-    uint32_t cap, const uint32_t *__restrict__ sort_err, float4 *__restrict__ acc, uint32_t acc_n4,
-    uint32_t *__restrict__ bwd_cnt, uint32_t *__restrict__ bwd_cls, int ntiles, int gy, int sb_nsbx, int sb_shift,
-    uint32_t seg_len, uint32_t *__restrict__ bin_base, uint32_t fseg_len, uint32_t *__restrict__ fctl, uint32_t fseg_min,
-    const uint32_t *__restrict__ longest, uint32_t *host_words, FwdSpin spin) {
+    uint32_t cap, const uint32_t *__restrict__ sort_err, uint32_t *__restrict__ bwd_cnt, uint32_t *__restrict__ bwd_cls,
+    int ntiles, uint32_t seg_len, uint32_t *__restrict__ bin_base, uint32_t fseg_len, uint32_t *__restrict__ fctl,
+    uint32_t fseg_min, FwdSpin spin) {
     GSR_KS(kKsRenderFwd);
     constexpr int kWaves = kPixPerLane / kSub;
     if (kdev && *kdev > cap) return;  // the point-list capacity is short: the host re-runs at K
-    if (host_words && blockIdx.x == 0 && threadIdx.x == 0) {
-        // the split gate's hints, written to pinned host memory here rather than by tile_order /
-        // sb_colscan: the PCIe store's completion is hidden in this long launch instead of ending
-        // a short one
-        __hip_atomic_store(host_words + kHostTileList, longest[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(host_words + kHostSBList, longest[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    if (GSR_FWD_ACC_CLEAR) {
-        // the backward's per-Gaussian accumulator rows (atomic mode) start at zero: every
-        // workgroup clears one slice with streaming stores that drain while it blends (the
-        // blend is VALU-bound; HBM is nearly idle here)
-        const uint32_t per = (acc_n4 + gridDim.x - 1) / gridDim.x;
-        const uint32_t a0 = blockIdx.x * per, a1 = min(acc_n4, a0 + per);
-        for (uint32_t k = a0 + threadIdx.x; k < a1; k += blockDim.x)
-        {
-            typedef float f4 __attribute__((ext_vector_type(4)));
-            if (GSR_ACC_NT) __builtin_nontemporal_store(f4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f4 *>(acc + k));
-            else acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
     __shared__ float4 s_a[kWaves][kWave];  // x, y, a_s, b_s (conic scaled for gauss_p2)
     __shared__ float4 s_b[kWaves][kWave];  // c_s, opacity, sub-block mask, list position + 1
     __shared__ float4 s_c[kWaves][kWave];  // r, g, b, 1 / depth
     __shared__ uint32_t s_work[kWaves];
 
-#if GSR_FWD_SEG_INKERNEL
-    // forward segments: the first kFwdWorkers workgroups are the worker pool (fwd_seg_worker)
-    uint32_t bidx = blockIdx.x;
-    if constexpr (kSub == 1) {
-        if (fseg_len) {
-            if (bidx < (uint32_t)kFwdWorkers) {
-                __shared__ uint32_t s_scalar[3];
-                uint64_t t_ready = 0, t_flags = 0;
-                fwd_seg_worker(ranges, point_list, W, H, gx, rec, bg, out_color, out_invd, final_T, n_contrib,
-                               tile_work, kdev ? *kdev : cap, sort_err, bwd_cnt, bwd_cls, ntiles, seg_len, fseg_len,
-                               bin_base, fctl, s_a[threadIdx.x >> 6], s_b[threadIdx.x >> 6], s_c[threadIdx.x >> 6],
-                               s_work, s_scalar, nullptr, spin, t_ready, t_flags);
-                return;
-            }
-            bidx -= (uint32_t)kFwdWorkers;
-        }
-    }
-#else
-    const uint32_t bidx = blockIdx.x;
-#endif
-
-    int tile, tx, ty;
-    if (sb_shift >= 0) {
-        // superblock launch order (GSR_FWD_SB_ORDER): fwd_order lists the SBs, a workgroup per SB
-        // tile slot; slots past the grid's edge have no tile
-        const uint32_t per = 1u << (2 * sb_shift), b = bidx;
-        const uint32_t k = fwd_order[b >> (2 * sb_shift)], t = b & (per - 1u);
-        tx = (int)(k % (uint32_t)sb_nsbx) * (1 << sb_shift) + (int)(t & ((1u << sb_shift) - 1u));
-        ty = (int)(k / (uint32_t)sb_nsbx) * (1 << sb_shift) + (int)(t >> sb_shift);
-        if (tx >= gx || ty >= gy) return;
-        tile = ty * gx + tx;
-    } else {
-        tile = (int)fwd_order[bidx];
-        tx = tile % gx;
-        ty = tile / gx;
-    }
+    const int tile = (int)fwd_order[blockIdx.x];  // launch order: tiles by descending list length
+    const int tx = tile % gx, ty = tile / gx;
     if (fseg_splits(ranges[tile].y - ranges[tile].x, fseg_min)) return;  // render_fwd_seg_kernel's tile
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int px = tx * kTile + (lane & 15);
     const int sy = ty * kTile + 4 * kSub * w;  // the wave's first pixel row
     const float pfx = (float)px;
-    // kPoly: the lane's offset from its sub-block's centre and its products (exact in fp32)
-    constexpr bool kPoly = GSR_FWD_POLY && kSub == 1;
-    const float lx = (float)(lane & 15) - 7.5f, ly = (float)(lane >> 4) - 1.5f;
-    const float lxx = lx * lx, lxy = lx * ly, lyy = ly * ly;
     const float tx0 = (float)(tx * kTile), sy0 = (float)sy;
 
     // liveness: kSub == 1 keeps a lane mask (no branches in the blend); otherwise a dead pixel's
@@ -644,7 +554,7 @@ __global__ __launch_bounds__(kWave * (kPixPerLane / kSub)) GSR_FWD_ATTR void ren
         alive[k] = px < W && py < H;
         amin[k] = alive[k] ? 1.0f / 255.0f : 2.f;
     }
-    uint64_t livem = __ballot(alive[0]);  // GSR_FWD_MASKSEL: the live pixels as a wave mask
+    uint64_t livem = __ballot(alive[0]);  // kSub == 1: the live pixels as a wave mask
     StatAcc fst;
     uint64_t fwd_acc = 0;
     const uint2 rg = ranges[tile];
@@ -666,7 +576,7 @@ __global__ __launch_bounds__(kWave * (kPixPerLane / kSub)) GSR_FWD_ATTR void ren
         uint32_t live = 0;  // sub-blocks with a pixel still accumulating (wave-uniform)
 #pragma unroll
         for (int k = 0; k < kSub; k++)
-            live |= (kSub == 1 && GSR_FWD_MASKSEL ? livem != 0 : __ballot(kSub == 1 ? alive[k] : amin[k] < 1.f) != 0)
+            live |= (kSub == 1 ? livem != 0 : __ballot(amin[k] < 1.f) != 0)
                         ? 1u << k
                         : 0u;
         if (!live) break;
@@ -691,19 +601,8 @@ __global__ __launch_bounds__(kWave * (kPixPerLane / kSub)) GSR_FWD_ATTR void ren
             const uint32_t slot = lane_prefix(keep);
             const uint32_t pos1 = base - rg.x + (uint32_t)lane + 1u;  // n_contrib counts list positions from 1
             const float as = qa.z * kHalfLog2e, bs = qa.w * kLog2e, cs = qb.x * kHalfLog2e;
-            if (kPoly) {
-                // the exponent as a quadratic in the pixel's offset (lx, ly) from the sub-block
-                // centre: p2 = F + D lx + E ly + a lx^2 - b lx ly + c ly^2
-                const float X = qa.x - (tx0 + 7.5f), Y = qa.y - (sy0 + 1.5f);
-                const float F = fmaf(-(bs * X), Y, fmaf(cs * Y, Y, (as * X) * X));
-                const float D = fmaf(bs, Y, (-2.f * as) * X);
-                const float E = fmaf(bs, X, (-2.f * cs) * Y);
-                s_a[w][slot] = make_float4(F, D, E, as);
-                s_b[w][slot] = make_float4(-bs, qb.y, cs, __uint_as_float(pos1));
-            } else {
-                s_a[w][slot] = make_float4(qa.x, qa.y, as, bs);
-                s_b[w][slot] = make_float4(cs, qb.y, __uint_as_float(m), __uint_as_float(pos1));
-            }
+            s_a[w][slot] = make_float4(qa.x, qa.y, as, bs);
+            s_b[w][slot] = make_float4(cs, qb.y, __uint_as_float(m), __uint_as_float(pos1));
             s_c[w][slot] = qc;
         }
         // wave-private LDS slice: the wave's own writes are visible after its lgkmcnt drain
@@ -714,19 +613,17 @@ __global__ __launch_bounds__(kWave * (kPixPerLane / kSub)) GSR_FWD_ATTR void ren
             const float4 b = s_b[w][j];
             const float4 c = s_c[w][j];
             const uint32_t mk = kSub > 1 ? __builtin_amdgcn_readfirstlane(__float_as_uint(b.z)) : 1u;
-            // kPoly: a = (F, D, E, a_s), b = (-b_s, opacity, c_s, position)
             const uint32_t pos = __float_as_uint(b.w);
-            const float dx = kPoly ? 0.f : a.x - pfx;
+            const float dx = a.x - pfx;
             const float adxdx_s = a.z * dx * dx;
             const float bdx_s = a.w * dx;
 #pragma unroll
             for (int k = 0; k < kSub; k++) {
                 if (kSub > 1 && !(mk & (1u << k))) continue;
                 const float dy = a.y - pfy[k];
-                const float p2 = kPoly ? fmaf(a.w, lxx, fmaf(b.x, lxy, fmaf(b.z, lyy, fmaf(a.y, lx, fmaf(a.z, ly, a.x)))))
-                                       : gauss_p2(adxdx_s, bdx_s, b.x, dy);
+                const float p2 = gauss_p2(adxdx_s, bdx_s, b.x, dy);
                 const float alpha = fminf(0.99f, b.y * gexp2(p2));
-                if (kSub == 1 && GSR_FWD_MASKSEL) {
+                if (kSub == 1) {
                     // the three tests as wave masks, combined on the scalar unit, and the three
                     // selects from one mask: one compare of test_T instead of two (the compiler
                     // materialises both the stop test and its negation)
@@ -749,13 +646,11 @@ __global__ __launch_bounds__(kWave * (kPixPerLane / kSub)) GSR_FWD_ATTR void ren
                     last[k] = __float_as_uint(lane_select(accm, b.w, __uint_as_float(last[k])));
                     continue;
                 }
-                const bool ok = kSub == 1 ? alive[k] && !(p2 > 0.0f) && !(alpha < 1.0f / 255.0f)
-                                          : !(p2 > 0.0f) && !(alpha < amin[k]);
+                const bool ok = !(p2 > 0.0f) && !(alpha < amin[k]);  // kSub > 1
                 const float test_T = T[k] * (1.f - alpha);
                 const bool cont = !(test_T < 0.0001f);
                 const bool accept = ok && cont;
-                if (kSub == 1) alive[k] = alive[k] && !(ok && !cont);
-                else amin[k] = ok && !cont ? 2.f : amin[k];
+                amin[k] = ok && !cont ? 2.f : amin[k];
                 const float wgt = accept ? alpha * T[k] : 0.f;
                 C0[k] = fmaf(c.x, wgt, C0[k]);
                 C1[k] = fmaf(c.y, wgt, C1[k]);
@@ -771,9 +666,9 @@ __global__ __launch_bounds__(kWave * (kPixPerLane / kSub)) GSR_FWD_ATTR void ren
         for (; j + 1 < cnt; j += 2) {
             blend(j);
             blend(j + 1);
-            if (GSR_FWD_EARLY_EXIT && !livem) break;  // every pixel of the sub-block has saturated
+            if (!livem) break;  // every pixel of the sub-block has saturated
         }
-        if (j < cnt && (!GSR_FWD_EARLY_EXIT || livem)) blend(j);
+        if (j < cnt && livem) blend(j);
         __builtin_amdgcn_wave_barrier();
     }
     if (GSR_BLEND_STATS) {
@@ -824,7 +719,7 @@ __global__ __launch_bounds__(kWave * (kPixPerLane / kSub)) GSR_FWD_ATTR void ren
     }
 }
 
-// render_bwd's tile with GSR_BWD_CLS: workgroup b takes the (b - first)-th tile of the class whose
+// render_bwd's tile: workgroup b takes the (b - first)-th tile of the class whose
 // range of launch positions holds b (class c covers [sum of counts below c, + count c)), from the
 // 256 class counts render_fwd left (4 per lane, one wave scan).
 __device__ __forceinline__ int bwd_tile_of(uint32_t b, const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ cls,
@@ -865,8 +760,7 @@ uint32_t set_fwd_split_min(uint32_t len) { return g_fseg_min.exchange(len); }
 // one 1024-thread workgroup buckets the T work estimates into 256 descending classes of
 // 2^shift instances (LDS histogram, scan, scatter).  Order within a class is arbitrary; every
 // tile writes only its own outputs, so results do not depend on it.
-__global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t *__restrict__ work, const uint2 *__restrict__ ranges,
-                                                          int T, int shift, uint32_t *__restrict__ order, const uint32_t *__restrict__ kdev, uint32_t cap,
+__global__ __launch_bounds__(1024) void tile_order_kernel(const uint2 *__restrict__ ranges, int T, int shift, uint32_t *__restrict__ order, const uint32_t *__restrict__ kdev, uint32_t cap,
                                                           uint32_t *__restrict__ zero_classes, uint32_t *__restrict__ fctl,
                                                           void *bin_base, uint32_t seg_len, uint32_t fseg_len,
                                                           uint32_t fseg_min, uint32_t *__restrict__ host_tilelist,
@@ -882,8 +776,7 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t *__rest
     if (threadIdx.x == 0) s_items = s_max = 0u;
     __syncthreads();
     auto bucket = [&](int t) {
-        const uint32_t wk = work ? work[t] : ranges[t].y - ranges[t].x;
-        const uint32_t k = wk >> shift;
+        const uint32_t k = (ranges[t].y - ranges[t].x) >> shift;
         return 255u - (k < 255u ? k : 255u);
     };
     // one pass over the tiles: the work histogram, the longest list (the split gate's hint) and,
@@ -894,7 +787,7 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t *__rest
     uint32_t mx = 0;
     for (int t = threadIdx.x; t < T; t += 1024) {
         const uint32_t len = ranges[t].y - ranges[t].x;
-        const uint32_t k = (work ? work[t] : len) >> shift;
+        const uint32_t k = len >> shift;
         atomicAdd(&hist[255u - (k < 255u ? k : 255u)], 1u);
         mx = max(mx, len);
         if (fseg_splits(len, fseg_min)) {
@@ -914,10 +807,7 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t *__rest
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (host_tilelist) {
-            if (GSR_HOST_WORDS == 2) *host_tilelist = s_max;  // a device word render_fwd forwards
-            else __hip_atomic_store(host_tilelist, s_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        if (host_tilelist) __hip_atomic_store(host_tilelist, s_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (fseg_len) {
             fctl[0] = s_items;  // kFwdItemsWord
             fctl[1] = 0u;       // kFwdNextWord
@@ -948,13 +838,13 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t *__rest
     for (int t = threadIdx.x; t < T; t += 1024) order[atomicAdd(&hist[bucket(t)], 1u)] = (uint32_t)t;
 }
 
-void launch_tile_order(const uint32_t *work, const uint2 *ranges, int T, int shift, uint32_t *order, hipStream_t s,
+void launch_tile_order(const uint2 *ranges, int T, int shift, uint32_t *order, hipStream_t s,
                        const uint32_t *kdev, uint32_t cap, uint32_t *zero_classes, uint32_t *fctl, void *bin_base,
                        uint32_t seg_len, uint32_t fseg_len, uint32_t *host_tilelist, uint32_t *fwd_ready, uint32_t fseg_min) {
     if (T == 0) return;
     // fseg_min: the frame's split minimum, computed once by the caller (render_fwd's skip test must see
     // the same value, or a tile could be skipped without being queued)
-    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, s, work, ranges, T, shift, order, kdev, cap, zero_classes,
+    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, s, ranges, T, shift, order, kdev, cap, zero_classes,
                        fctl, bin_base, seg_len, fctl ? fseg_len : 0u, fctl && fseg_len ? fseg_min : 0u,
                        host_tilelist, fwd_ready);
 }
@@ -962,7 +852,7 @@ void launch_tile_order(const uint32_t *work, const uint2 *ranges, int T, int shi
 static void launch_workers(const Camera &cam, const GeomState &gs, const BinningState &bs, const ImageState &is,
                            const float *bg, float *out_color, float *out_invdepth, bool need_bwd, uint32_t seg_len,
                            uint32_t fseg_len, hipStream_t ws, const uint32_t *ready, FwdSpin spin, int grid) {
-    uint32_t *const bcnt = GSR_BWD_CLS && need_bwd ? is.bwd_cnt : nullptr;
+    uint32_t *const bcnt = need_bwd ? is.bwd_cnt : nullptr;
     hipLaunchKernelGGL(render_fwd_seg_kernel, dim3(grid), dim3(kWave * kPixPerLane), 0, ws, is.ranges,
                        bs.point_list, cam.W, cam.H, cam.gx, gs.rec, bg, out_color, out_invdepth, is.final_T,
                        is.n_contrib, is.tile_work, bs.kdev, bs.cap, bs.kdev ? dsort_err_word(gs) : nullptr, bcnt,
@@ -973,7 +863,7 @@ static void launch_workers(const Camera &cam, const GeomState &gs, const Binning
 void launch_render_fwd_workers(const Camera &cam, const GeomState &gs, const BinningState &bs, const ImageState &is,
                                const float *bg, float *out_color, float *out_invdepth, bool need_bwd, uint32_t seg_len,
                                uint32_t fseg_len, hipStream_t ws, const uint32_t *ready, FwdSpin spin) {
-    if (cam.gx * cam.gy == 0 || !fseg_len || GSR_FWD_SUB != 1 || GSR_FWD_SEG_INKERNEL) return;
+    if (cam.gx * cam.gy == 0 || !fseg_len || GSR_FWD_SUB != 1) return;
     launch_workers(cam, gs, bs, is, bg, out_color, out_invdepth, need_bwd, seg_len, fseg_len, ws, ready, spin,
                    kFwdPoolWorkers);
 }
@@ -984,7 +874,7 @@ constexpr int kFwdCleanupWorkers = 64;
 void launch_render_fwd_cleanup(const Camera &cam, const GeomState &gs, const BinningState &bs, const ImageState &is,
                                const float *bg, float *out_color, float *out_invdepth, bool need_bwd, uint32_t seg_len,
                                uint32_t fseg_len, hipStream_t s, FwdSpin spin) {
-    if (cam.gx * cam.gy == 0 || !fseg_len || GSR_FWD_SUB != 1 || GSR_FWD_SEG_INKERNEL) return;
+    if (cam.gx * cam.gy == 0 || !fseg_len || GSR_FWD_SUB != 1) return;
     launch_workers(cam, gs, bs, is, bg, out_color, out_invdepth, need_bwd, seg_len, fseg_len, s, nullptr, spin,
                    kFwdCleanupWorkers);
 }
@@ -1001,25 +891,20 @@ void set_fwd_spin_limits(uint32_t ready, uint32_t flag) {
 
 void launch_render_fwd(const Camera &cam, const GeomState &gs, const BinningState &bs, const ImageState &is,
                        const float *bg, float *out_color, float *out_invdepth, hipStream_t s, bool need_bwd,
-                       bool sb_order, uint32_t seg_len, uint32_t fseg_len, hipStream_t worker_stream,
-                       bool workers_launched, const uint32_t *longest, uint32_t *host_words, uint32_t fseg_min,
-                       FwdSpin spin) {
+                       uint32_t seg_len, uint32_t fseg_len, hipStream_t worker_stream, bool workers_launched,
+                       uint32_t fseg_min, FwdSpin spin) {
     const int T = cam.gx * cam.gy;
     if (T == 0) return;
-    const SBGrid &sg = gs.sb;
-    if (sb_order || GSR_FWD_SUB != 1) fseg_len = 0;
-    const int grid = (sb_order ? sg.nsb << (2 * sg.shift) : T) + (GSR_FWD_SEG_INKERNEL && fseg_len ? kFwdWorkers : 0);
-    if (fseg_len && !GSR_FWD_SEG_INKERNEL && !workers_launched)
+    if (GSR_FWD_SUB != 1) fseg_len = 0;
+    if (fseg_len && !workers_launched)
         launch_workers(cam, gs, bs, is, bg, out_color, out_invdepth, need_bwd, seg_len, fseg_len,
                        worker_stream ? worker_stream : s, nullptr, spin, kFwdPoolWorkers);
     // launch order: is.tile_ids (rasterizer.hip, by list length)
 #define GSR_FWD_LAUNCH(K, NT)                                                                                       \
-    hipLaunchKernelGGL(K, dim3(grid), dim3(NT), 0, s, is.ranges, bs.point_list, cam.W, cam.H, cam.gx, gs.rec, bg,   \
+    hipLaunchKernelGGL(K, dim3(T), dim3(NT), 0, s, is.ranges, bs.point_list, cam.W, cam.H, cam.gx, gs.rec, bg,      \
                        out_color, out_invdepth, is.final_T, is.n_contrib, is.tile_work, is.tile_ids, bs.kdev, bs.cap, \
-                       bs.kdev ? dsort_err_word(gs) : nullptr, gs.acc, (uint32_t)(4 * (size_t)gs.nacc),              \
-                       GSR_BWD_CLS && need_bwd ? is.bwd_cnt : nullptr, is.bwd_cls, T, cam.gy, sg.nsbx,        \
-                       sb_order ? sg.shift : -1, seg_len, bs.point_list, fseg_len, is.bwd_cnt + kFwdItemsWord,       \
-                       fseg_len ? fseg_min : 0u, longest, longest ? host_words : nullptr, spin)
+                       bs.kdev ? dsort_err_word(gs) : nullptr, need_bwd ? is.bwd_cnt : nullptr, is.bwd_cls, T,       \
+                       seg_len, bs.point_list, fseg_len, is.bwd_cnt + kFwdItemsWord, fseg_len ? fseg_min : 0u, spin)
     static_assert(GSR_FWD_SUB == 1 || GSR_FWD_SUB == 2 || GSR_FWD_SUB == 4, "GSR_FWD_SUB: 1, 2 or 4");
     GSR_FWD_LAUNCH(render_fwd_kernel<GSR_FWD_SUB>, kWave * (kPixPerLane / GSR_FWD_SUB));
 #undef GSR_FWD_LAUNCH
@@ -1036,20 +921,8 @@ void launch_render_fwd(const Camera &cam, const GeomState &gs, const BinningStat
 // Sub-blocks an instance cannot touch (ellipse box, or past the sub-block's last contributor) are
 // skipped with a scalar branch on the wave-uniform mask: 0.479 vs 0.502 ms for the predicated
 // form on the 1M-Gaussian 1080p bench scene once tiles run heaviest-first.
-#ifndef GSR_BWD_BG_IN_S
-#define GSR_BWD_BG_IN_S 1  // 0: upstream's separate background term (one more FMA per pixel)
-#endif
 #ifndef GSR_BWD_WAVES_PER_EU
 #define GSR_BWD_WAVES_PER_EU 4  // 4 waves per SIMD: the instance pairs would otherwise take 129 VGPRs (3 waves)
-#endif
-#ifndef GSR_TILE_REVERSE
-#define GSR_TILE_REVERSE 0
-#endif
-#ifndef GSR_BWD_HALVES
-#define GSR_BWD_HALVES 1  // 0: halves added per instance (5.5 KiB of LDS, 29 instead of 17 waves per CU): 0.2259 -> 0.2333 ms (r03f)
-#endif
-#ifndef GSR_REC_PAD
-#define GSR_REC_PAD 1  // write the unused 4th float4 of a 64-B record (full 64-B segments)
 #endif
 struct BwdBatch {
     float4 a, b, c;  // GRec q0..q2
@@ -1092,7 +965,7 @@ __device__ __forceinline__ void bwd_zero_slice(const ZeroRows &zr) {
 }
 
 // kAtomic (default): every live instance's ten sums are added into its Gaussian's accumulator row
-// (GeomState.acc) with no-return float atomics once per batch -- ten wave-wide atomic instructions,
+// (BwdScratch.acc) with no-return float atomics once per batch -- ten wave-wide atomic instructions,
 // lanes = (instance, value) pairs, so each instance is ONE contiguous 40-B segment of a 64-B row
 // (one memory-side request; MI355X_MICROARCH.md, Global float atomics).  Otherwise each instance
 // writes a 64-B record at its Gaussian-major index and the tile's boundary key, and
@@ -1102,7 +975,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
     const uint2 *__restrict__ ranges, const uint32_t *__restrict__ point_list, int W, int H, int gx,
     const GRec *__restrict__ rec, const float *__restrict__ bg, const float *__restrict__ final_Ts,
     const uint32_t *__restrict__ n_contrib, const float *__restrict__ dL_dpix, const float *__restrict__ dL_dinvd,
-    const uint32_t *__restrict__ tile_order, const uint32_t *__restrict__ goff, uint64_t *__restrict__ boundary,
+    const uint32_t *__restrict__ goff, uint64_t *__restrict__ boundary,
     float4 *__restrict__ out, ZeroRows zr, const uint32_t *__restrict__ bwd_cnt, const uint32_t *__restrict__ bwd_cls,
     uint32_t ntiles, uint32_t seg_len, const float *__restrict__ ck, const uint32_t *__restrict__ seg_items) {
     GSR_KS(kKsRenderBwd);
@@ -1114,21 +987,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
     __shared__ float4 s_b[kWave];  // c_s, opacity, list position << 4 | sub-block mask, id / record index
     __shared__ float4 s_c[kWave];  // r, g, b, 1 / depth
     // per compacted instance: the two half-wave partials of its 10 sums, added once per batch
-    // (GSR_BWD_HALVES = 0: the halves added per instance, half the LDS -- 29 instead of 17 waves per
-    // CU -- but two more VALU per instance: slower, the kernel is issue-bound, not latency-bound)
-    __shared__ float s_red[kWave * 10 * (GSR_BWD_HALVES ? 2 : 1)];
-    __shared__ float4 s_d[GSR_BWD_HALVES ? kWave : 1];  // GSR_BWD_HALVES: conic a, b, c for the epilogue
+    __shared__ float s_red[kWave * 10 * 2];
+    __shared__ float4 s_d[kWave];  // conic a, b, c for the epilogue
 
     // Tiles run heaviest first (longest-processing-time order from the forward's per-tile work):
     // with ~2.7 tiles per wave slot, index order leaves a tail of a few heavy tiles.
     // With segments (seg_len != 0) the full segments render_fwd listed run first, then the class
     // lists; workgroups past both only zero their share of the gradient rows.
-    int item;
-    if (GSR_TILE_REVERSE) item = (int)blockIdx.x;
-    else if (GSR_BWD_CLS) {
-        const uint32_t nsg = seg_len ? bwd_cnt[kBwdSegCount] : 0u;
-        item = blockIdx.x < nsg ? (int)seg_items[blockIdx.x] : bwd_tile_of(blockIdx.x - nsg, bwd_cnt, bwd_cls, (int)ntiles);
-    } else item = (int)tile_order[blockIdx.x];
+    const uint32_t nsg = seg_len ? bwd_cnt[kBwdSegCount] : 0u;
+    const int item =
+        blockIdx.x < nsg ? (int)seg_items[blockIdx.x] : bwd_tile_of(blockIdx.x - nsg, bwd_cnt, bwd_cls, (int)ntiles);
     if (item < 0) {
         bwd_zero_slice(zr);
         return;
@@ -1148,7 +1016,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
     // The background is the layer behind the last contributor (alpha 1, colour bg): S starts at
     // bg . dL/dpix, which folds upstream's -T_final (bg . dL/dpix) / (1 - alpha) term into
     // T (cd - S) -- T_i S_i then carries T_final bg / (1 - alpha_i) by the same recurrence.
-    float S[kPixPerLane], pfy[kPixPerLane], TfB[kPixPerLane];
+    float S[kPixPerLane], pfy[kPixPerLane];
     uint32_t last[kPixPerLane], lastk[kPixPerLane];
     uint32_t maxlast = 0;
     // every per-pixel input load first (clamped to the image, zeroed outside it), so the 24 loads
@@ -1174,8 +1042,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
         dp1[k] = inside ? dp1[k] : 0.f;
         dp2[k] = inside ? dp2[k] : 0.f;
         did[k] = inside ? did[k] : 0.f;
-        S[k] = GSR_BWD_BG_IN_S ? fmaf(b2, dp2[k], fmaf(b1, dp1[k], b0 * dp0[k])) : 0.f;
-        TfB[k] = GSR_BWD_BG_IN_S ? 0.f : -T[k] * (b0 * dp0[k] + b1 * dp1[k] + b2 * dp2[k]);
+        S[k] = fmaf(b2, dp2[k], fmaf(b1, dp1[k], b0 * dp0[k]));
         lastk[k] = wave_max_u32(last[k]);  // sub-block k needs list positions < lastk[k]
         maxlast = lastk[k] > maxlast ? lastk[k] : maxlast;
     }
@@ -1207,8 +1074,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
     const float sx = 0.5f * (float)W, sy = 0.5f * (float)H;
     const int rs_slot = wave_rs10_slot(lane);
     const int rs20_slot = wave_rs20_slot(lane);
-    (void)rs_slot;
-    (void)rs20_slot;
     StatAcc bst;
     uint64_t b_inst = 0, b_batches = 0;
 
@@ -1248,7 +1113,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
             out[4 * (size_t)u + 0] = z;
             out[4 * (size_t)u + 1] = z;
             out[4 * (size_t)u + 2] = z;
-            if (GSR_REC_PAD) out[4 * (size_t)u + 3] = z;
+            out[4 * (size_t)u + 3] = z;  // the unused 4th float4 too: full 64-B segments
         }
         const uint64_t keep = __ballot(m != 0u);
         const uint32_t cnt = (uint32_t)__popcll(keep);
@@ -1261,7 +1126,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
             s_a[slot] = make_float4(qa.x, qa.y, qa.z * kHalfLog2e, qa.w * kLog2e);  // scaled conic: gauss_p2
             s_b[slot] = make_float4(qb.x * kHalfLog2e, qb.y, __uint_as_float(pos << 4 | m), __uint_as_float(u));
             s_c[slot] = qc;
-            if (GSR_BWD_HALVES) s_d[slot] = make_float4(qa.z, qa.w, qb.x, 0.f);
+            s_d[slot] = make_float4(qa.z, qa.w, qb.x, 0.f);
         }
         __syncthreads();
         // one compacted instance's replay over its sub-blocks: the ten lane sums q (dx moments
@@ -1299,7 +1164,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
                 if (kDepth) cd = fmaf(c.w, did[k], cd);
                 const float dlac = cd - S[k];
                 S[k] = fmaf(ae, dlac, S[k]);
-                const float dla = GSR_BWD_BG_IN_S ? dlac * T[k] : fmaf(TfB[k], rc, dlac * T[k]);
+                const float dla = dlac * T[k];
                 // u = G dL/dalpha: the conic / mean terms are opacity * u times (dx, dy) moments,
                 // summed here as sum u, sum u dy, sum u dy^2 (dx is the lane's column: applied
                 // once per instance below; opacity and the conic after the wave sum)
@@ -1329,33 +1194,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
             using I3 = std::integral_constant<int, 3>;
             using First = std::true_type;
             using Next = std::false_type;
-#ifndef GSR_BWD_FULLSWITCH
-#define GSR_BWD_FULLSWITCH 0  // measured: 0.2257 -> 0.249 ms (r03j A/B), the larger basic blocks did not pay
-#endif
             // scalar branches on the wave-uniform mask: sub-blocks the instance cannot touch are
-            // skipped.  GSR_BWD_FULLSWITCH: one case per mask, so all of an instance's active
-            // sub-blocks are one basic block and their independent p2 -> exp -> alpha -> rcp -> T
-            // chains interleave (nested ifs put every sub-block in a block of its own: each chain's
-            // latency was exposed)
-            if (GSR_BWD_FULLSWITCH) {
-                switch (mk) {
-                    case 1: pix(I0{}, First{}); break;
-                    case 2: pix(I1{}, First{}); break;
-                    case 3: pix(I0{}, First{}); pix(I1{}, Next{}); break;
-                    case 4: pix(I2{}, First{}); break;
-                    case 5: pix(I0{}, First{}); pix(I2{}, Next{}); break;
-                    case 6: pix(I1{}, First{}); pix(I2{}, Next{}); break;
-                    case 7: pix(I0{}, First{}); pix(I1{}, Next{}); pix(I2{}, Next{}); break;
-                    case 8: pix(I3{}, First{}); break;
-                    case 9: pix(I0{}, First{}); pix(I3{}, Next{}); break;
-                    case 10: pix(I1{}, First{}); pix(I3{}, Next{}); break;
-                    case 11: pix(I0{}, First{}); pix(I1{}, Next{}); pix(I3{}, Next{}); break;
-                    case 12: pix(I2{}, First{}); pix(I3{}, Next{}); break;
-                    case 13: pix(I0{}, First{}); pix(I2{}, Next{}); pix(I3{}, Next{}); break;
-                    case 14: pix(I1{}, First{}); pix(I2{}, Next{}); pix(I3{}, Next{}); break;
-                    default: pix(I0{}, First{}); pix(I1{}, Next{}); pix(I2{}, Next{}); pix(I3{}, Next{}); break;
-                }
-            } else
+            // skipped
             switch (__builtin_ctz(mk)) {
                 case 0:
                     pix(I0{}, First{});
@@ -1387,62 +1227,39 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
         // 23.5 instead of 26 VALU per instance, one LDS park per pair); a lone last instance takes
         // wave_rs10.  The sums' bits are the same either way (same partners, same order).
         uint32_t j = 0;
-#ifndef GSR_BWD_PAIRS
-#define GSR_BWD_PAIRS 1
-#endif
-        if (GSR_BWD_PAIRS && GSR_BWD_HALVES) {
-            for (; j + 1 < cnt; j += 2) {
-                float qa[10], qb[10];
-                const bool anya = replay(j, qa);
-                const bool anyb = replay(j + 1, qb);
-                const float h = __any(anya || anyb) ? wave_rs20(qa, qb, lane) : 0.f;
-                if (rs20_slot >= 0) s_red[((j + (rs20_slot >= 10 ? 1u : 0u)) * 2 + (lane >> 5)) * 10 + rs20_slot % 10] = h;
-            }
+        for (; j + 1 < cnt; j += 2) {
+            float qa[10], qb[10];
+            const bool anya = replay(j, qa);
+            const bool anyb = replay(j + 1, qb);
+            const float h = __any(anya || anyb) ? wave_rs20(qa, qb, lane) : 0.f;
+            if (rs20_slot >= 0) s_red[((j + (rs20_slot >= 10 ? 1u : 0u)) * 2 + (lane >> 5)) * 10 + rs20_slot % 10] = h;
         }
         for (; j < cnt; j++) {
             float q[10];
             const bool any = replay(j, q);
             // reduce-scatter: lane `rs_slot` of rows 1 and 3 parks its half-wave partial; the two
             // halves are added once per batch below instead of per instance
-            float h = __any(any) ? wave_rs10(q, lane) : 0.f;
-            if (GSR_BWD_HALVES) {
-                if ((lane & 16) && rs_slot >= 0) s_red[(j * 2 + (lane >> 5)) * 10 + rs_slot] = h;
-            } else {
-                // the two halves added here (lanes l and l ^ 32 hold them): one sum per instance
-                const auto hs = __builtin_amdgcn_permlane32_swap(__float_as_uint(h), __float_as_uint(h), false, false);
-                h = __uint_as_float(hs[0]) + __uint_as_float(hs[1]);
-                if (lane < 16 && rs_slot >= 0) s_red[j * 10 + rs_slot] = h;
-            }
+            const float h = __any(any) ? wave_rs10(q, lane) : 0.f;
+            if ((lane & 16) && rs_slot >= 0) s_red[(j * 2 + (lane >> 5)) * 10 + rs_slot] = h;
         }
         __syncthreads();
         float r[10];
-        // GSR_BWD_HALVES: the epilogue in slot order (lane < cnt); otherwise in the batch's own lane
-        // order (its instance's conic, opacity and id are still in this lane's registers)
-        const bool ep = GSR_BWD_HALVES ? (uint32_t)lane < cnt : m != 0u;
-        const uint32_t es = GSR_BWD_HALVES ? (uint32_t)lane : slot;
+        // the epilogue in slot order: lane es adds the two halves of compacted instance es
+        const bool ep = (uint32_t)lane < cnt;
+        const uint32_t es = (uint32_t)lane;
         if (ep) {
-            if (GSR_BWD_HALVES) {
-                const float2 *d = reinterpret_cast<const float2 *>(s_red) + es * 10;
+            const float2 *d = reinterpret_cast<const float2 *>(s_red) + es * 10;
 #pragma unroll
-                for (int t = 0; t < 5; t++) {
-                    const float2 p0 = d[t], p1 = d[5 + t];
-                    r[2 * t] = p0.x + p1.x;
-                    r[2 * t + 1] = p0.y + p1.y;
-                }
-            } else {
-                const float2 *d = reinterpret_cast<const float2 *>(s_red) + es * 5;
-#pragma unroll
-                for (int t = 0; t < 5; t++) {
-                    const float2 p = d[t];
-                    r[2 * t] = p.x;
-                    r[2 * t + 1] = p.y;
-                }
+            for (int t = 0; t < 5; t++) {
+                const float2 p0 = d[t], p1 = d[5 + t];
+                r[2 * t] = p0.x + p1.x;
+                r[2 * t + 1] = p0.y + p1.y;
             }
-            const size_t o = 4 * (size_t)(GSR_BWD_HALVES ? __float_as_uint(s_b[es].w) : u);
+            const size_t o = 4 * (size_t)__float_as_uint(s_b[es].w);
             {
                 // moments -> (dmean2D, dconic): dL/dG = opacity dL/dalpha, dG/d(dx) = -G (a dx + b dy), ...
-                const float4 id = GSR_BWD_HALVES ? s_d[es] : make_float4(qa.z, qa.w, qb.x, 0.f);
-                const float op = GSR_BWD_HALVES ? s_b[es].y : qb.y, ca = id.x, cb = id.y, cc = id.z;
+                const float4 id = s_d[es];
+                const float op = s_b[es].y, ca = id.x, cb = id.y, cc = id.z;
                 const float m0 = r[0], m1 = r[1], mxx = r[2], mxy = r[3], myy = r[4];
                 r[0] = -op * fmaf(cb, m1, ca * m0);
                 r[1] = -op * fmaf(cb, m0, cc * m1);
@@ -1461,7 +1278,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
                 out[o + 0] = make_float4(r[0], r[1], r[2], r[3]);
                 out[o + 1] = make_float4(r[4], r[5], r[6], r[7]);
                 out[o + 2] = make_float4(r[8], r[9], 0.f, 0.f);
-                if (GSR_REC_PAD) out[o + 3] = make_float4(0.f, 0.f, 0.f, 0.f);
+                out[o + 3] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
         if (kAtomic) {
@@ -1469,7 +1286,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
             // read its halves), then ten atomic instructions: lane l of round k adds value
             // (64k + l) % 10 of instance (64k + l) / 10 -- consecutive lanes, consecutive floats
             // of one Gaussian's row
-            if (GSR_BWD_HALVES) __syncthreads();  // otherwise each lane rewrites the slot it read
+            __syncthreads();
             float *st = s_red;
             if (ep) {
 #pragma unroll
@@ -1497,10 +1314,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVE
     }
 }
 
-bool fwd_segments_supported() { return GSR_FWD_SUB == 1 && !GSR_FWD_SB_ORDER; }
-bool fwd_segments_in_kernel() { return GSR_FWD_SEG_INKERNEL != 0; }
+bool fwd_segments_supported() { return GSR_FWD_SUB == 1; }
 
-bool bwd_segments_supported() { return GSR_BWD_CLS && GSR_FWD_SUB == 1 && GSR_BWD_BG_IN_S && !GSR_TILE_REVERSE; }
+bool bwd_segments_supported() { return GSR_FWD_SUB == 1; }
 
 void launch_render_bwd(const Camera &cam, const GeomState &gs, const BinningState &bs, const ImageState &is,
                        const int *radii, const float *bg, const float *dL_dpix, const float *dL_dinvdepth,
@@ -1518,9 +1334,8 @@ void launch_render_bwd(const Camera &cam, const GeomState &gs, const BinningStat
     const unsigned grid = (unsigned)bwd_grid(T, bs.cap, seg_len);
 #define GSR_BWD_LAUNCH(D, A)                                                                                       \
     hipLaunchKernelGGL((render_bwd_kernel<D, A>), dim3(grid), dim3(kWave), 0, s, is.ranges, bs.point_list, cam.W,   \
-                       cam.H, cam.gx, gs.rec, bg, is.final_T, is.n_contrib, dL_dpix, dL_dinvdepth, is.tile_order,    \
-                       gs.offsets, is.boundary, A ? sc.acc : sc.rec, z, is.bwd_cnt, is.bwd_cls, (uint32_t)T, seg_len, \
-                       ck, items)
+                       cam.H, cam.gx, gs.rec, bg, is.final_T, is.n_contrib, dL_dpix, dL_dinvdepth, gs.offsets,       \
+                       is.boundary, A ? sc.acc : sc.rec, z, is.bwd_cnt, is.bwd_cls, (uint32_t)T, seg_len, ck, items)
     if (dL_dinvdepth) {
         if (sc.atomic) GSR_BWD_LAUNCH(true, true);
         else GSR_BWD_LAUNCH(true, false);

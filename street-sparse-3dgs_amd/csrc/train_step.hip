@@ -139,12 +139,6 @@ int fail_step(int rc, const char *what) {
 
 // The rasterizer and the activation backward read the raw parameters and activate them where they
 // are used (GaussianInputs.raw); the Python-driven step writes the activations in a launch of their own.
-#ifndef GSR_STEP_FUSE_ACT
-#define GSR_STEP_FUSE_ACT 1
-#endif
-#ifndef GSR_STEP_PHOTO_IN_SSIM
-#define GSR_STEP_PHOTO_IN_SSIM 1  // 0: the SSIM pass writes G and the exposure backward forms the gradient
-#endif
 
 int invalid(const char *msg) {
     set_last_error(std::string("gsr_train_step: ") + msg);
@@ -273,7 +267,7 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
         bool photo = false;  // the SSIM pass wrote the photometric gradient itself (gsr_launch.h)
         if ((rc = step_loss_forward(image, a->gt, H, W, a->lambda_dssim, loss_scratch, gmap, invd,
                                     depth ? a->mono_invdepth : nullptr, a->depth_mask, a->depth_weight,
-                                    depth_scratch, d_invd, a->losses, flag, s, GSR_STEP_PHOTO_IN_SSIM ? one : nullptr,
+                                    depth_scratch, d_invd, a->losses, flag, s, one,
                                     a->alpha_mask, &photo)))
             return fail_step(rc, "losses");
 
@@ -292,8 +286,8 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
     // the activation backward (skybox lock, relevance flag, densification statistics:
     // train_single.py:193-194, 217-223) fused into the rasterizer backward's live-row pass, which
     // then writes the raw parameters' gradients itself (gsr_launch.h StepAct); the conditions
-    // mirror backward.hip's split path (GSR_STEP_FUSE_ACT=0: the separate activation backward)
-    const bool fuse_act = GSR_STEP_FUSE_ACT && sparse_rows && a->M == 16 &&
+    // mirror backward.hip's split path (otherwise: the separate activation backward)
+    const bool fuse_act = sparse_rows && a->M == 16 &&
                           (reinterpret_cast<uintptr_t>(a->features) & 15u) == 0 &&
                           (reinterpret_cast<uintptr_t>(a->features_grad) & 15u) == 0;
     const StepAct act{a->scaling, a->opacity, reinterpret_cast<const float4 *>(a->rotation), a->skybox_rows, radii,

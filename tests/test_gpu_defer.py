@@ -1,5 +1,5 @@
 """The forward queues its binning and render before reading K when it has a capacity hint from the
-previous frame (csrc/rasterizer.hip, GSR_DEFER_K).  A frame whose K exceeds that capacity is
+previous frame (csrc/rasterizer.hip, the deferred K read).  A frame whose K exceeds that capacity is
 binned and rendered again at K: its outputs and gradients must equal those of the same frame
 rendered with enough capacity, bit for bit."""
 from __future__ import annotations

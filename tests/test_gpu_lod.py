@@ -52,9 +52,9 @@ def test_lod_cut_matches_oracle(tau, vp):
 
 @pytest.mark.parametrize("leaves,offset", [(600, 0), (5000, 1), (70_000, 3)])
 def test_lod_cut_ragged_tiles_and_unaligned_nodes(leaves, offset):
-    """The one-pass cut (lod.hip lod_cut_kernel: 1024-node tiles, nodes staged through LDS, a decoupled
-    lookback for the offsets) on one ragged tile, on several, and with the nodes array starting
-    `offset` rows into its buffer (28-B rows: not 16-B aligned, the staging's dword path) --
+    """The cut (lod.hip: lod_cut_count_kernel's per-tile counts, records and sums over 1024-node tiles,
+    lod_cut_write_kernel's offsets from the group and tile sums) on one ragged tile, on several, and
+    with the nodes array starting `offset` rows into its buffer (28-B rows: not 16-B aligned) --
     bit-exact with the oracle."""
     import gs_oracle as O
     from gs_train.synthetic import synthetic_lod_hierarchy, tau_threshold

@@ -3,6 +3,11 @@
 #   bash tools/ab_c5.sh <tag> <rounds> <variant>...
 # variant: "default" (the in-tree library), a library path, or NAME=VALUE[,NAME=VALUE]@<library or default>
 # (environment settings for that run)
+# Every run's JSON line lands in the tag's output directory ($O below) as <variant>.<round>.json (config5.ms_per_frame,
+# config5.raster_stages_ms, config5.split_ms; "value" is the metric line).
+# What the two retired special-case scripts did:
+#   every vlibs/c5_*.so against the default, two rounds:  bash tools/ab_c5.sh c5lib 2 default vlibs/c5_*.so
+#   one variant library against the default, two rounds:  bash tools/ab_c5.sh c5ab 2 default vlibs/<variant>.so
 set -u -o pipefail
 TAG=$1; R=$2; shift 2
 O=gpurun_out/$TAG; mkdir -p "$O"
