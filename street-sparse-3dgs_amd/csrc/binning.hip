@@ -8,9 +8,12 @@
 //   level 1  Gaussian -> superblock (SB = 2^s x 2^s tiles, ~500 at 1080p).  Chunks of 1024 (more when P is large)
 //            depth-ordered Gaussians count their SB footprints in LDS (sb_count), per-SB column
 //            scans over chunks give every chunk its offsets (sb_colscan, sb_base), and a second
-//            pass writes each SB's Gaussian list in depth order (sb_scatter): per batch of 64
-//            Gaussians, each lane ORs its bit into an LDS lane mask per SB it covers, and its
-//            rank in an SB's list is the popcount of the lower lanes of that mask.
+//            pass writes each SB's Gaussian list in depth order (sb_scatter): per round of 512
+//            Gaussians (one per lane of 8 waves), each lane ORs its bit into its wave's LDS mask
+//            word of every SB it covers, one thread per SB turns the 8 words into prefixes, and a
+//            lane's rank in an SB's list is the SB's position + its wave's prefix + the popcount
+//            of the lower lanes of its wave's word.  Both kernels walk a footprint by row and
+//            column (SBWalk): no division per cell.
 //   level 2  SB -> tiles (tile_bin): one workgroup per SB counts its tiles' instances, writes the
 //            tile ranges, and re-walks the SB list with the same lane-mask ranking per tile to
 //            place every instance at its stable position.
@@ -61,13 +64,12 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-#ifndef GSR_SCATTER_WAVES
-#define GSR_SCATTER_WAVES 8
-#endif
 #ifndef GSR_SMALL_SB
 #define GSR_SMALL_SB 16
 #endif
-constexpr int kScatterWaves = GSR_SCATTER_WAVES;
+constexpr int kScatterWaves = 8;  // sb_scatter: one 64-bit mask word and one 16-bit prefix per wave and SB
+constexpr int kScatterRows = 64 * kScatterWaves;  // depth-ordered rows per round
+constexpr size_t kScatterLdsPerSB = kScatterWaves * (sizeof(uint64_t) + sizeof(uint16_t)) + sizeof(uint32_t);  // 84 B
 constexpr int kSmallSB = GSR_SMALL_SB;
 
 struct SBFoot {
@@ -84,14 +86,48 @@ __device__ __forceinline__ SBFoot sb_foot(const TileRect &r, int shift) {
     return f;
 }
 
-__device__ __forceinline__ uint32_t sb_key(const SBFoot &f, int k, int nsbx) {
-    return (uint32_t)((f.sy0 + k / f.sw) * nsbx + f.sx0 + k % f.sw);
-}
+// Walk over a footprint's superblocks in row-major order (cell k = row k / sw, column k % sw),
+// stepped by row and column so that no cell costs a division: sx runs from sx0 to sx0 + sw - 1,
+// then the next sy, and the SB key sy * nsbx + sx is kept alongside.
+struct SBWalk {
+    int sx, sy, sx0, sw, nsbx;
+    uint32_t key;
+    // cell 0
+    __device__ __forceinline__ SBWalk(const SBFoot &f, int nsbx_)
+        : sx(f.sx0), sy(f.sy0), sx0(f.sx0), sw(f.sw), nsbx(nsbx_), key((uint32_t)(f.sy0 * nsbx_ + f.sx0)) {}
+    // cell k0 (the wave-wide walks' lane start: the one division)
+    __device__ __forceinline__ SBWalk(const SBFoot &f, int nsbx_, int k0) : SBWalk(f, nsbx_) {
+        const int dy = k0 / f.sw, dx = k0 - dy * f.sw;
+        sx += dx;
+        sy += dy;
+        key += (uint32_t)(dy * nsbx_ + dx);
+    }
+    __device__ __forceinline__ void next() {
+        sx++;
+        key++;
+        if (sx == sx0 + sw) {
+            sx = sx0;
+            sy++;
+            key += (uint32_t)(nsbx - sw);
+        }
+    }
+    // dy rows and dx < sw columns ahead (a wave-wide walk's 64 cells: dy = 64 / sw, dx = 64 % sw)
+    __device__ __forceinline__ void skip(int dy, int dx) {
+        sx += dx;
+        sy += dy;
+        key += (uint32_t)(dy * nsbx + dx);
+        if (sx >= sx0 + sw) {
+            sx -= sw;
+            sy++;
+            key += (uint32_t)(nsbx - sw);
+        }
+    }
+};
 
-// footprint clipped to SB `key`, in SB-local tile coordinates (8 bits each)
-__device__ __forceinline__ uint32_t sb_local(const TileRect &r, uint32_t key, const SBGrid &sg) {
+// footprint clipped to SB (sx, sy), in SB-local tile coordinates (8 bits each)
+__device__ __forceinline__ uint32_t sb_local(const TileRect &r, int sx, int sy, const SBGrid &sg) {
     const int side = 1 << sg.shift;
-    const int ox = (int)(key % (uint32_t)sg.nsbx) * side, oy = (int)(key / (uint32_t)sg.nsbx) * side;
+    const int ox = sx << sg.shift, oy = sy << sg.shift;
     return (uint32_t)(max(r.x0, ox) - ox) | ((uint32_t)(max(r.y0, oy) - oy) << 8) |
            ((uint32_t)(min(r.x1, ox + side - 1) - ox) << 16) | ((uint32_t)(min(r.y1, oy + side - 1) - oy) << 24);
 }
@@ -132,12 +168,11 @@ __global__ __launch_bounds__(1024) void sb_count_kernel(int P, SBGrid sg, const 
     const int j0 = chunk * sg.chunk, j1 = min(pv, j0 + sg.chunk);
     const int side = 1 << sg.shift;
     // instances of Gaussian footprint r in SB `key`
-    const auto count = [&](const TileRect &r, uint32_t key) {
-        const int sx = (int)(key % (uint32_t)sg.nsbx), sy = (int)(key / (uint32_t)sg.nsbx);
-        const int h = min(r.y1, sy * side + side - 1) - max(r.y0, sy * side) + 1;
-        const int w = min(r.x1, sx * side + side - 1) - max(r.x0, sx * side) + 1;
-        atomicAdd(&cg[key], 1u);
-        atomicAdd(&ci[key], (uint32_t)(w * h));
+    const auto count = [&](const TileRect &r, const SBWalk &c) {
+        const int h = min(r.y1, c.sy * side + side - 1) - max(r.y0, c.sy * side) + 1;
+        const int w = min(r.x1, c.sx * side + side - 1) - max(r.x0, c.sx * side) + 1;
+        atomicAdd(&cg[c.key], 1u);
+        atomicAdd(&ci[c.key], (uint32_t)(w * h));
     };
     for (int jb = j0; jb < j1; jb += 1024) {
         const int j = jb + (int)threadIdx.x;
@@ -146,12 +181,15 @@ __global__ __launch_bounds__(1024) void sb_count_kernel(int P, SBGrid sg, const 
         // footprints over more than kSmallSB superblocks are counted by the whole wave, one SB per
         // lane (a single lane would hold its wave for hundreds of iterations)
         const bool small = f.n <= kSmallSB;
-        for (int k = 0; small && k < f.n; k++) count(r, sb_key(f, k, sg.nsbx));
+        SBWalk c(f, sg.nsbx);
+        for (int k = 0; small && k < f.n; k++, c.next()) count(r, c);
         for (uint64_t big = __ballot(!small); big; big &= big - 1) {
             const int b = __ffsll((unsigned long long)big) - 1;
             const SBFoot fb = lane_foot(f, b);
             const TileRect rb = lane_rect(r, b);
-            for (int k = threadIdx.x & 63; k < fb.n; k += 64) count(rb, sb_key(fb, k, sg.nsbx));
+            const int dy = 64 / fb.sw, dx = 64 - dy * fb.sw;
+            SBWalk cb(fb, sg.nsbx, (int)(threadIdx.x & 63));
+            for (int k = threadIdx.x & 63; k < fb.n; k += 64, cb.skip(dy, dx)) count(rb, cb);
         }
     }
     __syncthreads();
@@ -319,155 +357,163 @@ __device__ __forceinline__ void mask_clear(uint64_t *m) {
     __hip_atomic_store(m, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// Level 1, pass 3: stable scatter of (chunk, wave, batch, lane)-ordered Gaussians into the SB
-// lists.  Ranks come from LDS lane masks: every lane ORs its bit into the mask of each SB it
-// covers, its rank in that SB's list is the popcount of the lower lanes, and the highest lane of
-// each mask advances the SB's position and clears the mask.  Footprints of up to kSmallSB SBs
-// are walked per lane; larger ones (rare, 3-sigma splats) by the whole wave, one at a time, so
-// one outlier does not serialise its batch.
-__global__ __launch_bounds__(64 * kScatterWaves) void sb_scatter_kernel(int P, SBGrid sg,
-                                                                         const uint32_t *__restrict__ order,
-                                                                         const uint2 *__restrict__ drect,
-                                                                         const uint32_t *__restrict__ drect4,
-                                                                         const uint32_t *__restrict__ col,
-                                                                         const uint32_t *__restrict__ base_g,
-                                                                         uint2 *__restrict__ sblist,
-                                                                         uint4 *__restrict__ sblist4,
-                                                                         const uint32_t *__restrict__ dkey,
-                                                                         const uint32_t *__restrict__ kdev, uint32_t cap,
-                                                                         const uint32_t *__restrict__ culled) {
+// Measurement builds only (GSR_SB_TRACE=1): per-workgroup phase stamps (s_memrealtime, 100 MHz)
+// of sb_sort_bin (local sort) or sb_scatter (global sort), read back with gsr_debug_trace.
+#ifndef GSR_SB_TRACE
+#define GSR_SB_TRACE 0
+#endif
+__device__ unsigned long long g_sb_trace[2048 * 8];
+#define SB_STAMP(slot)                                                                         \
+    do {                                                                                       \
+        if (GSR_SB_TRACE && threadIdx.x == 0 && blockIdx.x < 2048) {                           \
+            __builtin_amdgcn_s_waitcnt(0);                                                     \
+            g_sb_trace[blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memrealtime();            \
+        }                                                                                      \
+    } while (0)
+
+// Level 1, pass 3: stable scatter of the chunk's depth-ordered rows into the SB lists, in rounds
+// of kScatterRows rows (one per lane; row = round start + 64 * wave + lane).  Per round:
+//   1. mark    every lane ORs its bit into mask[wave][s] of each SB s its footprint covers
+//   2. prefix  one thread per SB turns the round's 8 mask words into exclusive popcount prefixes
+//              (16 bits each: at most kScatterRows) and moves the SB's position on by the total
+//   3. write   position = the SB's position before the round + prefix[wave][s] + the popcount of
+//              the lower lanes of mask[wave][s] (the prefixes are stored less the round's total,
+//              so "before the round" needs no copy of the position)
+//   4. clear   the masks, when another round follows
+// LDS per SB: 8 x 8 B of masks ([wave][nsb], so the prefix threads read consecutive words and a
+// wave only marks its own plane), 8 x 2 B of prefixes, 4 B of position = 84 B.  Footprints of up
+// to kSmallSB SBs are walked per lane; larger ones (rare, 3-sigma splats) by the whole wave, one
+// at a time with the owning lane's bit, so one outlier does not serialise its round.
+__global__ __launch_bounds__(kScatterRows) void sb_scatter_kernel(int P, SBGrid sg,
+                                                                  const uint32_t *__restrict__ order,
+                                                                  const uint2 *__restrict__ drect,
+                                                                  const uint32_t *__restrict__ drect4,
+                                                                  const uint32_t *__restrict__ col,
+                                                                  const uint32_t *__restrict__ base_g,
+                                                                  uint2 *__restrict__ sblist,
+                                                                  uint4 *__restrict__ sblist4,
+                                                                  const uint32_t *__restrict__ dkey,
+                                                                  const uint32_t *__restrict__ kdev, uint32_t cap,
+                                                                  const uint32_t *__restrict__ culled) {
     GSR_KS(kKsSbScatter);
     // the point-list capacity is short: the host re-runs at K (SB instances <= K, so K <= cap
     // bounds the level-1 lists too; the same test as every other binning / render kernel)
     if (*kdev > cap) return;
     const int chunk = chunk_of_block(blockIdx.x);
     if (chunk >= visible_chunks(sg, P, culled)) return;  // culled rows only, or the XCD group's padding
-    extern __shared__ uint32_t wc[];  // [W][nsb] per-wave running positions, then [W][nsb] u64 masks
+    extern __shared__ __attribute__((aligned(16))) unsigned char sc[];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int nsb = sg.nsb;
-    for (int i = threadIdx.x; i < 3 * kScatterWaves * nsb; i += 64 * kScatterWaves) wc[i] = 0u;
-    __syncthreads();
-    const int per_wave = sg.chunk / kScatterWaves;
+    uint64_t *const planes = reinterpret_cast<uint64_t *>(sc);                           // [wave][nsb] masks
+    uint4 *const pre = reinterpret_cast<uint4 *>(sc + sizeof(uint64_t) * kScatterWaves * (size_t)nsb);  // [nsb][wave] u16
+    const int16_t *const pre16 = reinterpret_cast<const int16_t *>(pre);
+    uint32_t *const run = reinterpret_cast<uint32_t *>(pre + nsb);                       // [nsb] position after the round
+    uint64_t *const msk = planes + w * nsb;
+    for (int i = threadIdx.x; i < kScatterWaves * nsb; i += kScatterRows) mask_clear(&planes[i]);
     const int pv = culled ? P - (int)min(*culled, (uint32_t)P) : P;  // slots past pv: not written by the sort
-    const int jw0 = chunk * sg.chunk + w * per_wave, jw1 = min(pv, jw0 + per_wave);
-    uint32_t *run = wc + w * nsb;
-    uint64_t *msk = reinterpret_cast<uint64_t *>(wc + kScatterWaves * nsb) + w * nsb;
+    const int j0 = chunk * sg.chunk, j1 = min(pv, j0 + sg.chunk);
     const uint64_t lt = (1ull << lane) - 1ull;
-    // the SB bases of this chunk (read after the counting): loads issued now
-    constexpr int kSBPerThread = (kMaxSB + 64 * kScatterWaves - 1) / (64 * kScatterWaves);
-    uint32_t sbase[kSBPerThread];
-#pragma unroll
-    for (int q = 0; q < kSBPerThread; q++) {
-        const int sq = (int)threadIdx.x + q * 64 * kScatterWaves;
-        sbase[q] = sq < nsb ? base_g[sq] + col[(size_t)sq * sg.ccols + cnt_col(sg, chunk)] : 0u;
-    }
-    // list loads one batch ahead of their use
-    const auto rect_at = [&](int j) { return j < jw1 ? load_drect(drect, drect4, j) : make_uint2(0u, 0u); };
-
-    // per-wave SB counts
-    uint2 rnext = rect_at(jw0 + lane);
-    for (int jb = jw0; jb < jw1; jb += 64) {
-        const TileRect r = unpack_rect(rnext);
-        rnext = rect_at(jb + 64 + lane);
-        const SBFoot f = sb_foot(r, sg.shift);
-        const bool small = f.n <= kSmallSB;
-#pragma unroll
-        for (int k = 0; k < kSmallSB; k++)
-            if (small && k < f.n) atomicAdd(&run[sb_key(f, k, sg.nsbx)], 1u);
-        for (uint64_t big = __ballot(!small); big; big &= big - 1) {
-            const int b = __ffsll((unsigned long long)big) - 1;
-            const SBFoot fb = lane_foot(f, b);
-            for (int k = lane; k < fb.n; k += 64) atomicAdd(&run[sb_key(fb, k, sg.nsbx)], 1u);
-        }
-    }
+    // the chunk's position in every SB list (read after the counting)
+    for (int s = threadIdx.x; s < nsb; s += kScatterRows)
+        run[s] = base_g[s] + col[(size_t)s * sg.ccols + cnt_col(sg, chunk)];
+    // list loads one round ahead of their use.  Local sort (sblist4): index order, and each entry
+    // carries the Gaussian's depth key (read here in index order, coalesced -- the sort kernel
+    // would otherwise gather it per entry)
+    const auto rect_at = [&](int j) { return j < j1 ? load_drect(drect, drect4, j) : make_uint2(0u, 0u); };
+    const auto id_at = [&](int j) { return j < j1 ? (order ? order[j] : (uint32_t)j) : 0u; };
+    const auto key_at = [&](int j) { return (sblist4 && j < j1) ? dkey[j] : 0u; };
+    const auto emit = [&](uint32_t at, uint32_t g, uint32_t loc, uint32_t gk) {
+        if (sblist4)
+            sblist4[at] = make_uint4(g, loc, gk, 0u);
+        else
+            sblist[at] = make_uint2(g, loc);
+    };
+    uint32_t gnext = id_at(j0 + (int)threadIdx.x), knext = key_at(j0 + (int)threadIdx.x);
+    uint2 rnext = rect_at(j0 + (int)threadIdx.x);
+    SB_STAMP(0);  // stamps 1-3 and 4-6: mark, prefix, write of the first two rounds (wave 0); 7: the end
     __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kSBPerThread; q++) {
-        const int s = (int)threadIdx.x + q * 64 * kScatterWaves;
-        if (s >= nsb) break;
-        uint32_t b = sbase[q];
-        for (int k = 0; k < kScatterWaves; k++) {
-            const uint32_t c = wc[k * nsb + s];
-            wc[k * nsb + s] = b;
-            b += c;
-        }
-    }
-    __syncthreads();
-
-    // local sort (sblist4): index order, and each entry carries the Gaussian's depth key (read
-    // here in index order, coalesced -- the sort kernel would otherwise gather it per entry)
-    const auto id_at = [&](int j) { return j < jw1 ? (order ? order[j] : (uint32_t)j) : 0u; };
-    const auto key_at = [&](int j) { return (sblist4 && j < jw1) ? dkey[j] : 0u; };
-    uint32_t gnext = id_at(jw0 + lane), knext = key_at(jw0 + lane);
-    rnext = rect_at(jw0 + lane);
-    for (int jb = jw0; jb < jw1; jb += 64) {
+    for (int jr = j0, rd = 0; jr < j1; jr += kScatterRows, rd++) {
         const uint32_t g = gnext, gk = knext;
         const TileRect r = unpack_rect(rnext);  // (0, 0) past the end: no tiles
-        gnext = id_at(jb + 64 + lane);
-        knext = key_at(jb + 64 + lane);
-        rnext = rect_at(jb + 64 + lane);
+        gnext = id_at(jr + kScatterRows + (int)threadIdx.x);
+        knext = key_at(jr + kScatterRows + (int)threadIdx.x);
+        rnext = rect_at(jr + kScatterRows + (int)threadIdx.x);
         const SBFoot f = sb_foot(r, sg.shift);
-        const bool small = f.n <= kSmallSB;
-        const uint64_t bigs = __ballot(!small);
-        // 1. masks
-#pragma unroll
-        for (int k = 0; k < kSmallSB; k++)
-            if (small && k < f.n) mask_or(&msk[sb_key(f, k, sg.nsbx)], 1ull << lane);
+        const int n = f.n <= kSmallSB ? f.n : 0;  // cells of the per-lane walk
+        const uint64_t bigs = __ballot(f.n > kSmallSB);
+        // 1. mark
+        {
+            SBWalk c(f, sg.nsbx);
+            for (int k = 0; k < n; k++, c.next()) mask_or(&msk[c.key], 1ull << lane);
+        }
         for (uint64_t big = bigs; big; big &= big - 1) {
             const int b = __ffsll((unsigned long long)big) - 1;
             const SBFoot fb = lane_foot(f, b);
-            for (int k = lane; k < fb.n; k += 64)
-                mask_or(&msk[sb_key(fb, k, sg.nsbx)], 1ull << b);
+            const int dy = 64 / fb.sw, dx = 64 - dy * fb.sw;
+            SBWalk c(fb, sg.nsbx, lane);
+            for (int k = lane; k < fb.n; k += 64, c.skip(dy, dx)) mask_or(&msk[c.key], 1ull << b);
         }
-        // 2. ranked writes
+        if (rd < 2) SB_STAMP(1 + 3 * rd);
+        __syncthreads();
+        // 2. prefix: run[s] moves on to the round's end, and the prefixes are stored relative to
+        // it (word k's exclusive prefix minus the round's total: -kScatterRows .. 0 in 16 bits)
+#pragma unroll 1
+        for (int s = threadIdx.x; s < nsb; s += kScatterRows) {
+            uint64_t m[kScatterWaves];
 #pragma unroll
-        for (int k = 0; k < kSmallSB; k++)
-            if (small && k < f.n) {
-                const uint32_t key = sb_key(f, k, sg.nsbx);
-                const uint32_t at = run[key] + (uint32_t)__popcll(mask_load(&msk[key]) & lt);
-                if (sblist4)
-                    sblist4[at] = make_uint4(g, sb_local(r, key, sg), gk, 0u);
-                else
-                    sblist[at] = make_uint2(g, sb_local(r, key, sg));
+            for (int k = 0; k < kScatterWaves; k++) m[k] = mask_load(&planes[k * nsb + s]);
+            uint32_t p[kScatterWaves], acc = 0;
+#pragma unroll
+            for (int k = 0; k < kScatterWaves; k++) {
+                p[k] = acc;
+                acc += (uint32_t)__popcll(m[k]);
             }
+#pragma unroll
+            for (int k = 0; k < kScatterWaves; k++) p[k] = (p[k] - acc) & 0xFFFFu;
+            pre[s] = make_uint4(p[0] | p[1] << 16, p[2] | p[3] << 16, p[4] | p[5] << 16, p[6] | p[7] << 16);
+            run[s] += acc;
+        }
+        if (rd < 2) SB_STAMP(2 + 3 * rd);
+        __syncthreads();
+        // 3. write: four cells at a time, their LDS reads issued together (cells past the
+        // footprint's end read its first SB and store nothing)
+        {
+            SBWalk c(f, sg.nsbx);
+            const uint32_t key0 = n ? c.key : 0u;
+            for (int k0 = 0; k0 < n; k0 += 4) {
+                uint32_t at[4], loc[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++, c.next()) {
+                    const uint32_t key = k0 + i < n ? c.key : key0;
+                    at[i] = run[key] + (uint32_t)(int)pre16[key * kScatterWaves + w] + (uint32_t)__popcll(mask_load(&msk[key]) & lt);
+                    loc[i] = sb_local(r, c.sx, c.sy, sg);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (k0 + i < n) emit(at[i], g, loc[i], gk);
+            }
+        }
         for (uint64_t big = bigs; big; big &= big - 1) {
             const int b = __ffsll((unsigned long long)big) - 1;
             const SBFoot fb = lane_foot(f, b);
             const TileRect rb = lane_rect(r, b);
             const uint32_t gb = (uint32_t)rl((int)g, b), gkb = (uint32_t)rl((int)gk, b);
-            for (int k = lane; k < fb.n; k += 64) {
-                const uint32_t key = sb_key(fb, k, sg.nsbx);
-                const uint32_t at = run[key] + (uint32_t)__popcll(mask_load(&msk[key]) & ((1ull << b) - 1ull));
-                if (sblist4)
-                    sblist4[at] = make_uint4(gb, sb_local(rb, key, sg), gkb, 0u);
-                else
-                    sblist[at] = make_uint2(gb, sb_local(rb, key, sg));
+            const int dy = 64 / fb.sw, dx = 64 - dy * fb.sw;
+            SBWalk c(fb, sg.nsbx, lane);
+            for (int k = lane; k < fb.n; k += 64, c.skip(dy, dx)) {
+                const uint32_t at = run[c.key] + (uint32_t)(int)pre16[c.key * kScatterWaves + w] +
+                                    (uint32_t)__popcll(mask_load(&msk[c.key]) & ((1ull << b) - 1ull));
+                emit(at, gb, sb_local(rb, c.sx, c.sy, sg), gkb);
             }
         }
-        // 3. the highest lane of every mask advances the SB position and clears the mask
-#pragma unroll
-        for (int k = 0; k < kSmallSB; k++)
-            if (small && k < f.n) {
-                const uint32_t key = sb_key(f, k, sg.nsbx);
-                const uint64_t m = mask_load(&msk[key]);
-                if (m != 0 && 63 - __clzll((long long)m) == lane) {
-                    run[key] += (uint32_t)__popcll(m);
-                    mask_clear(&msk[key]);
-                }
-            }
-        for (uint64_t big = bigs; big; big &= big - 1) {
-            const int b = __ffsll((unsigned long long)big) - 1;
-            const SBFoot fb = lane_foot(f, b);
-            for (int k = lane; k < fb.n; k += 64) {
-                const uint32_t key = sb_key(fb, k, sg.nsbx);
-                const uint64_t m = mask_load(&msk[key]);
-                if (m != 0 && 63 - __clzll((long long)m) == b) {
-                    run[key] += (uint32_t)__popcll(m);
-                    mask_clear(&msk[key]);
-                }
-            }
-        }
+        if (rd < 2) SB_STAMP(3 + 3 * rd);
+        // 4. clear
+        if (jr + kScatterRows >= j1) break;
+        __syncthreads();
+        for (int i = threadIdx.x; i < kScatterWaves * nsb; i += kScatterRows) mask_clear(&planes[i]);
+        __syncthreads();
     }
+    SB_STAMP(7);
 }
 
 // Level 2: one workgroup per SB; wave w owns a contiguous 1/kTBWaves of the SB's list (entries
@@ -711,20 +757,6 @@ __device__ __forceinline__ uint64_t lanes_with_digit(uint32_t d, uint64_t valid)
     }
     return m;
 }
-
-// Measurement builds only (GSR_SB_TRACE=1): per-workgroup phase stamps (s_memrealtime, 100 MHz)
-// of sb_sort_bin, read back with gsr_debug_trace.
-#ifndef GSR_SB_TRACE
-#define GSR_SB_TRACE 0
-#endif
-__device__ unsigned long long g_sb_trace[2048 * 8];
-#define SB_STAMP(slot)                                                                         \
-    do {                                                                                       \
-        if (GSR_SB_TRACE && threadIdx.x == 0 && blockIdx.x < 2048) {                           \
-            __builtin_amdgcn_s_waitcnt(0);                                                     \
-            g_sb_trace[blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memrealtime();            \
-        }                                                                                      \
-    } while (0)
 
 // __launch_bounds__(1024, 8): registers budgeted for 8 waves per SIMD -- two 1024-thread
 // workgroups per CU (66 KiB of LDS each); at the compiler's default (7 waves per SIMD, 104 SGPRs)
@@ -1016,10 +1048,10 @@ void launch_binning_scatter(int P, const Camera &cam, const GeomState &gs, const
                             hipStream_t s) {
     const SBGrid &sg = gs.sb;
     if (P == 0 || cam.gx * cam.gy == 0) return;
-    const size_t l3 = sizeof(uint32_t) * 3 * kScatterWaves * (size_t)sg.nsb;
+    const size_t l3 = kScatterLdsPerSB * (size_t)sg.nsb;
     const uint2 *rects = index_order ? gs.rect8 : gs.drect;
     const uint32_t *rects4 = index_order ? gs.rect4 : drect4_of(gs);
-    hipLaunchKernelGGL(sb_scatter_kernel, dim3(sb_blocks(sg)), dim3(64 * kScatterWaves), l3, s, P, sg,
+    hipLaunchKernelGGL(sb_scatter_kernel, dim3(sb_blocks(sg)), dim3(kScatterRows), l3, s, P, sg,
                        index_order ? (const uint32_t *)nullptr : gs.order, rects, rects4, gs.sb_cnt_g, gs.sb_base_g,
                        bs.sblist, index_order ? bs.sblist4 : (uint4 *)nullptr, gs.dkey, bs.kdev, bs.cap,
                        index_order ? (const uint32_t *)nullptr : dsort_culled_word(gs));

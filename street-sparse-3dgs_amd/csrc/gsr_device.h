@@ -524,7 +524,7 @@ constexpr int kSBChunk = GSR_SB_CHUNK;  // smallest level-1 chunk (SBGrid.chunk 
 #define GSR_MAX_CHUNKS 3072  // config 5 (7.4M): 3072 -> bin_superblocks 0.40 ms, 1536 -> 0.43, 768 -> 0.51
 #endif
 constexpr int kMaxChunks = GSR_MAX_CHUNKS;  // chunks before SBGrid.chunk doubles
-constexpr int kMaxSB = 1536;          // superblocks (3 x 8 waves x 4 B of LDS each in sb_scatter)
+constexpr int kMaxSB = 1536;          // superblocks (84 B of LDS each in sb_scatter: 8 x 8 B masks, 8 x 2 B prefixes, 4 B position)
 constexpr int kMaxTilesPerSB = 256;   // up to 16 x 16 tiles per superblock
 // Level 2 of long superblock lists (tile_bin split, binning.hip): an SB list longer than
 // GSR_TB_SPLIT entries is binned in up to kTBMaxSlices slices by tb_split_kernel's work items
