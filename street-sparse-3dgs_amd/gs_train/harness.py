@@ -353,7 +353,7 @@ class TrainStep:
 
 def make_problem(P, W, H, n_views=4, seed=0, sh_degree=3, device="cuda", step_cls=None, perturb=0.02,
                  depth=True, depth_mask_frac=0.85, alpha=False, skybox_points=0, scaffold_points=0, fovx_deg=60.0,
-                 depth_only=0, iterations=LR["iterations"]):
+                 depth_only=0, iterations=LR["iterations"], world=None):
     """A synthetic Street-sparse training problem: ground-truth views and inverse-depth maps
     rendered from a seeded scene over `n_views` orbit cameras, depth masks (a random ~85% of each
     map valid, as the reference's depth_mask), optional alpha masks, and a step (TrainStep, or
@@ -361,11 +361,18 @@ def make_problem(P, W, H, n_views=4, seed=0, sh_degree=3, device="cuda", step_cl
     The mono depth maps are the true inverse depth with 5% multiplicative noise.  fovx_deg: 90 for
     Street-sparse's cube faces (ss_utils/generate_colmap_calibration.py:476-479: f = size / 2).
     depth_only: the last `depth_only` views are depth-only (no target image; a LiDAR-like map: the
-    true inverse depth on a random 30% of the pixels, zero elsewhere)."""
+    true inverse depth on a random 30% of the pixels, zero elsewhere).
+    world: (scene, cameras) in place of the seeded scene around the origin and its orbit cameras: a
+    synthetic_scene-style dict of P Gaussians and n_views camera tuples as synthetic.camera returns."""
     from .synthetic import orbit_cameras, synthetic_scene
     step_cls = step_cls or TrainStep
-    s = synthetic_scene(P, W, H, seed=seed, sh_degree=sh_degree, fovx_deg=fovx_deg)
-    cams = orbit_cameras(n_views, W, H, fovx_deg=fovx_deg)
+    if world is None:
+        s = synthetic_scene(P, W, H, seed=seed, sh_degree=sh_degree, fovx_deg=fovx_deg)
+        cams = orbit_cameras(n_views, W, H, fovx_deg=fovx_deg)
+    else:
+        s, cams = world
+        if s["means3D"].shape[0] != P or len(cams) != n_views:
+            raise ValueError("make_problem: world must hold P Gaussians and n_views cameras")
     truth = GaussianSet(s["means3D"], s["shs"], s["opacities"], s["scales"], s["rotations"], n_images=n_views,
                         sh_degree=sh_degree, device=device, joined_features=True)
     tmp = TrainStep(truth, cams, [None] * n_views, W, H)

@@ -78,6 +78,18 @@ def test_native_step_with_depth_only_views_equals_python_step(skybox, alpha):
     """A view cycle of three photometric and two depth-only views: the native step (depth-only
     branch: no SSIM / exposure pass, zero colour gradient, exposure gradient zeroed, no exposure
     step) is bit-identical to the Python-driven step, which zeroes the SH gradients explicitly."""
+    _native_step_with_depth_only_views(skybox, alpha, n_views=5, depth_only=2, steps=7, photometric_steps=5.0)
+
+
+def test_native_step_with_depth_only_views_equals_python_step_steep_poses():
+    """The same over two steep-posed cameras (posed_cases.steep_world), the second one depth-only:
+    its inverse depth is the view matrix's third column at work, no longer (0, 0, 1, 0)."""
+    import posed_cases as PC
+    _native_step_with_depth_only_views(300, True, n_views=2, depth_only=1, steps=5, photometric_steps=3.0,
+                                       world=PC.steep_world(20_000, 256, 192, 1))
+
+
+def _native_step_with_depth_only_views(skybox, alpha, n_views, depth_only, steps, photometric_steps, world=None):
     from helpers import deterministic
     from gs_train.harness import make_problem
     from gs_train.native_step import NativeTrainStep
@@ -85,10 +97,10 @@ def test_native_step_with_depth_only_views_equals_python_step(skybox, alpha):
     with deterministic():
         for native in (False, True):
             torch.manual_seed(0)
-            ts = make_problem(20_000, 256, 192, n_views=5, seed=1, step_cls=NativeTrainStep if native else None,
-                              depth=True, alpha=alpha, skybox_points=skybox, depth_only=2)
+            ts = make_problem(20_000, 256, 192, n_views=n_views, seed=1, step_cls=NativeTrainStep if native else None,
+                              depth=True, alpha=alpha, skybox_points=skybox, depth_only=depth_only, world=world)
             torch.manual_seed(3)
-            losses = torch.stack([ts.step().clone() for _ in range(7)])
+            losses = torch.stack([ts.step().clone() for _ in range(steps)])
             out[native] = (losses, _snapshot(ts),
                            [ts.exposure_optimizer.state[ts.g._exposure][k].clone() for k in ("exp_avg", "exp_avg_sq")],
                            float(ts.exposure_optimizer.state[ts.g._exposure]["step"]))
@@ -98,8 +110,11 @@ def test_native_step_with_depth_only_views_equals_python_step(skybox, alpha):
     for x, y in zip(ea, eb):
         assert torch.equal(x, y)
     # 7 steps over [p, p, p, d, d, p, p]: the exposure optimizer stepped on the 5 photometric ones
-    assert esa == esb == 5.0
-    assert sa[2] == [7.0] * 5
+    # (two steep views, 5 steps over [p, d, p, d, p]: 3)
+    assert esa == esb == photometric_steps
+    assert sa[2] == [float(steps)] * 5
+    if world is not None:  # the posed frames render: the steps saw Gaussians
+        assert float(sa[3][2].sum()) > 0.5 * steps * 20_000
 
 
 def test_depth_only_step_matches_reference_structured_step():

@@ -155,10 +155,17 @@ def check_record_offsets(S, vis, K):
         np.testing.assert_array_equal(off[1:], off[:-1] + n[:-1])
 
 
-def compare(c, st, g, h, check_grads=True, global_sort=False):
+def compare(c, st, g, h, check_grads=True, global_sort=False, subsets=None):
+    """subsets: {name: row mask} (posed_cases.subsets): every gradient tensor is also held to GRAD_TOL
+    over the rows of each mask alone, and the SH clamp flags (one byte per row, bit ch set when
+    channel ch clamped at zero: preprocess.hip) equal the oracle's on every row with radii > 0."""
     assert h["K"] == st["K"], f"K {h['K']} vs oracle {st['K']}"
     np.testing.assert_array_equal(h["radii"], st["radii"])
     S = h["state"]
+    if subsets is not None:
+        on = st["radii"] > 0
+        want = (st["clamped"].reshape(-1, 3).astype(np.uint8) << np.arange(3, dtype=np.uint8)).sum(1).astype(np.uint8)
+        np.testing.assert_array_equal(S["clamped"][on], want[on])
     np.testing.assert_array_equal(S["tiles_touched"], st["tiles_touched"])
     np.testing.assert_array_equal(S["keys"], st["keys"])
     np.testing.assert_array_equal(S["point_list"], st["point_list"])
@@ -207,6 +214,10 @@ def compare(c, st, g, h, check_grads=True, global_sort=False):
             err = rel_l2(G[hk].reshape(g[ok].shape), g[ok])
             margins["grad_" + hk] = err
             assert err <= GRAD_TOL, f"{c['name']}: grad {hk} rel L2 {err}"
+            for name, m in (subsets or {}).items():
+                err = rel_l2(G[hk].reshape(g[ok].shape)[m], g[ok][m])
+                margins[f"grad_{hk}@{name}"] = err
+                assert err <= GRAD_TOL, f"{c['name']}: grad {hk} over the {int(m.sum())} {name} rows rel L2 {err}"
     finally:
         record_margins(c["name"], **margins)
     return
@@ -282,26 +293,32 @@ def test_local_sort_paths_and_fallback():
         np.testing.assert_array_equal(a[4], b[4])
 
 
-@pytest.mark.gpu
-def test_precomputed_paths_and_cross_identity():
-    """colors_precomp / cov3D_precomp paths against the oracle, and the cross-path identity
-    pinned by reference code: rasterizing (shs, scales, rotations) equals rasterizing the
-    reference's python paths (eval_sh + 0.5 clamp, get_covariance) -- SURVEY.md 8(c)(ii)."""
+def precomputed_inputs(s, deg):
+    """The reference's python paths in fp64: (colors_precomp from eval_sh + 0.5 clamped at zero,
+    cov3D_precomp from get_covariance), as float32 arrays."""
     import dense_torch as DT
     import torch
-    c = dict(name="precomp", P=1500, W=96, H=64, deg=3, seed=11, log_scale=-3.0)
-    s = make_scene(c)
-    dcol, dinv = upstream_grads(c)
     means = torch.tensor(s["means3D"], dtype=torch.float64)
     d = means - torch.tensor(s["campos"], dtype=torch.float64)
     d = d / d.norm(dim=1, keepdim=True)
-    colors = torch.clamp_min(DT.eval_sh_t(3, torch.tensor(s["shs"], dtype=torch.float64), d) + 0.5, 0.0)
+    colors = torch.clamp_min(DT.eval_sh_t(deg, torch.tensor(s["shs"], dtype=torch.float64), d) + 0.5, 0.0)
     colors = colors.float().numpy()
     L = DT.quat_to_R(torch.tensor(s["rotations"], dtype=torch.float64)) * torch.tensor(
         s["scales"], dtype=torch.float64)[:, None, :]
     S3 = (L @ L.transpose(1, 2)).numpy()
     cov = np.stack([S3[:, 0, 0], S3[:, 0, 1], S3[:, 0, 2], S3[:, 1, 1], S3[:, 1, 2], S3[:, 2, 2]], 1)
-    cov = cov.astype(np.float32)
+    return colors, cov.astype(np.float32)
+
+
+@pytest.mark.gpu
+def test_precomputed_paths_and_cross_identity():
+    """colors_precomp / cov3D_precomp paths against the oracle, and the cross-path identity
+    pinned by reference code: rasterizing (shs, scales, rotations) equals rasterizing the
+    reference's python paths (eval_sh + 0.5 clamp, get_covariance) -- SURVEY.md 8(c)(ii)."""
+    c = dict(name="precomp", P=1500, W=96, H=64, deg=3, seed=11, log_scale=-3.0)
+    s = make_scene(c)
+    dcol, dinv = upstream_grads(c)
+    colors, cov = precomputed_inputs(s, 3)
     st, g = run_oracle(s, c, dcol, dinv, colors_precomp=colors, cov3D_precomp=cov)
     h = run_hip(s, c, dcol, dinv, colors_precomp=colors, cov3D_precomp=cov)
     compare(c, st, g, h)

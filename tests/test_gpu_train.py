@@ -290,6 +290,18 @@ def test_native_step_equals_python_step(depth, alpha, skybox, scaffold):
     (harness.TrainStep): the same entry points in the same order, so with the deterministic
     backward every parameter, Adam moment, exposure, densification statistic and loss value is
     bit-identical after several steps over cycled views."""
+    _native_step_equals_python_step(depth, alpha, skybox, scaffold, n_views=3)
+
+
+def test_native_step_equals_python_step_steep_poses():
+    """The same over two steep-posed cameras (posed_cases.steep_world): the fused live-row backward
+    under a view rotation, a translation and a campos that the orbit cameras' 4 degrees barely move
+    from the identity; test_gpu_posed.py holds the Python-driven step's rasterizer to the oracle."""
+    import posed_cases as PC
+    _native_step_equals_python_step(True, True, 300, 0, n_views=2, world=PC.steep_world(20_000, 256, 192, 1))
+
+
+def _native_step_equals_python_step(depth, alpha, skybox, scaffold, n_views, world=None):
     from helpers import deterministic
     from gs_train.harness import make_problem
     from gs_train.native_step import NativeTrainStep
@@ -298,8 +310,8 @@ def test_native_step_equals_python_step(depth, alpha, skybox, scaffold):
     with deterministic():
         for native in (False, True):
             torch.manual_seed(0)
-            ts = make_problem(20_000, 256, 192, n_views=3, seed=1, step_cls=NativeTrainStep if native else None,
-                              depth=depth, alpha=alpha, skybox_points=skybox, scaffold_points=scaffold)
+            ts = make_problem(20_000, 256, 192, n_views=n_views, seed=1, step_cls=NativeTrainStep if native else None,
+                              depth=depth, alpha=alpha, skybox_points=skybox, scaffold_points=scaffold, world=world)
             if scaffold:
                 with torch.no_grad():
                     ts.g._scaling[scaffold - 50:scaffold + 50] += 3.0
@@ -321,6 +333,8 @@ def test_native_step_equals_python_step(depth, alpha, skybox, scaffold):
     assert sa == sb == [4.0] * 5
     for x, y in zip(ta, tb):
         assert torch.equal(x, y)
+    if world is not None:  # the posed frames render: the steps saw Gaussians and moved them
+        assert float(ta[2].sum()) > 0.5 * 4 * 20_000 and bool(torch.isfinite(la).all())
 
 
 @pytest.mark.parametrize("dense_rows", ["0", "1"])

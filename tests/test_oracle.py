@@ -60,7 +60,9 @@ def _fwd(s, W, H, deg, **kw):
 DENSE_CASES = [
     dict(P=300, W=64, H=48, seed=3, deg=3, log_scale=-2.5),
     dict(P=600, W=70, H=50, seed=4, deg=1, log_scale=-2.7),
-    dict(P=400, W=64, H=64, seed=5, deg=2, log_scale=-2.6, spread=1.8),   # 1.3*tanfov clamp active
+    dict(P=400, W=64, H=64, seed=5, deg=2, log_scale=-2.6, spread=1.8),   # means out to 1.8*tanfov, but none
+    # of the rows past the 1.3*tanfov clamp reaches a pixel (posed_cases.subsets: 0 `beyond` rows): the clamp's
+    # backward is carried by POSED_DENSE_CASES' steep_all below
     dict(P=400, W=80, H=48, seed=6, deg=0, log_scale=-2.4, mod=1.6),      # scale_modifier != 1
     dict(P=400, W=64, H=48, seed=8, deg=3, log_scale=-2.5, primx=0.35, primy=0.6),
 ]
@@ -88,10 +90,71 @@ def test_oracle_backward_matches_fp64_autograd(c):
         assert rel_l2(b[ok].reshape(d[dk].shape), d[dk]) < 5e-5, dk
 
 
+FP64_PAIRS = [("dL_dmeans3D", "dL_dmeans3D"), ("dL_dmeans2D", "dL_dmeans2D"), ("dL_dopacities", "dL_dopacity"),
+              ("dL_dshs", "dL_dsh"), ("dL_dscales", "dL_dscales"), ("dL_drotations", "dL_drotations")]
+
+# Posed cameras and the clamp populations (tests/posed_cases.py): the identity camera of the cases
+# above hides the view rotation, the translation row, campos and the off-diagonal projection entries
+POSED_DENSE_CASES = [
+    dict(name="steep_plain", pose="steep", P=450, W=64, H=48, seed=31, deg=3, log_scale=-2.5),
+    # splats of a pixel or more and a larger opaque share: a 500-row scene then holds 20 capped rows
+    dict(name="steep_all", pose="steep", P=500, W=70, H=50, seed=34, deg=2, log_scale=-1.5, primx=0.35, primy=0.6,
+         edge=0.3, opaque=0.4, dark=2.0),
+    dict(name="cam1", pose="cam1", P=400, W=96, H=64, seed=33, deg=3, log_scale=-2.5),
+    dict(name="steep_modifier", pose="steep", P=400, W=64, H=48, seed=34, deg=1, log_scale=-2.6, mod=1.6),
+]
+
+
+def _posed(c):
+    import posed_cases as PC
+    s = PC.make_scene(c)
+    st = _fwd(s, c["W"], c["H"], c["deg"], shs=s["shs"], scales=s["scales"], rotations=s["rotations"],
+              scale_modifier=c.get("mod", 1.0))
+    return s, st
+
+
+@pytest.mark.parametrize("c", POSED_DENSE_CASES, ids=[c["name"] for c in POSED_DENSE_CASES])
+def test_oracle_backward_matches_fp64_autograd_posed(c):
+    """The oracle against fp64 autograd under posed cameras, with the 1.3 * tanfov clamp, the 0.99
+    alpha cap and the SH colour clamp populated; the bars of the identity-camera test, applied to
+    every tensor and again to the rows of each population alone (posed_cases.subsets)."""
+    import posed_cases as PC
+    W, H = c["W"], c["H"]
+    s, st = _posed(c)
+    rng = np.random.default_rng(0)
+    gc = rng.normal(size=(3, H, W))
+    gd = rng.normal(size=(1, H, W))
+    b = O.backward(st, gc, gd, true_scale_grad=True)
+    d = DT.dense_grads(st, gc, gd)
+    masks = PC.subsets(s, st)
+    PC.assert_populated(masks, b, PC.claims(c))
+    assert int((st["radii"] > 0).sum()) > 0.5 * c["P"]
+    assert rel_l2(st["color"], d["color"]) < 1e-5
+    assert rel_l2(st["invdepth"], d["invdepth"]) < 1e-5
+    for dk, ok in FP64_PAIRS:
+        got, ref = b[ok].reshape(d[dk].shape), d[dk]
+        assert rel_l2(got, ref) < 5e-5, dk
+        for name in PC.claimed_subsets(c):
+            m = masks[name]
+            assert rel_l2(got[m], ref[m]) < 5e-5, (dk, name, int(m.sum()))
+
+
 def test_oracle_precomputed_paths_match_fp64_autograd():
+    _precomputed_paths_match_fp64_autograd(posed=False)
+
+
+def test_oracle_precomputed_paths_match_fp64_autograd_posed():
+    _precomputed_paths_match_fp64_autograd(posed=True)
+
+
+def _precomputed_paths_match_fp64_autograd(posed):
     W, H = 64, 48
-    s = _scene(400, W, H, 9, 3, -2.5)
-    colors = np.random.default_rng(1).uniform(0, 1, (400, 3)).astype(np.float32)
+    if posed:  # steep camera, rows past the 1.3 * tanfov clamp and capped alphas
+        import posed_cases as PC
+        s = PC.make_scene(dict(pose="steep", P=400, W=W, H=H, seed=9, log_scale=-2.5, edge=0.3, opaque=0.2))
+    else:
+        s = _scene(400, W, H, 9, 3, -2.5)
+    colors =np.random.default_rng(1).uniform(0, 1, (400, 3)).astype(np.float32)
     cov = O.cov3d(s["scales"], s["rotations"])
     st = _fwd(s, W, H, 3, colors_precomp=colors, cov3D_precomp=cov)
     rng = np.random.default_rng(2)
@@ -190,9 +253,22 @@ def test_torch_splat_baseline_matches_oracle(P, W, H, deg, mod):
     an independent formulation -- upstream's exp(power), tensor ops, torch.autograd -- and must
     render and differentiate the same frame as the C oracle: radii bit-exact, PSNR >= 100 dB,
     gradients within 1e-4 relative L2."""
+    _torch_splat_matches_oracle(O.synthetic_scene(P, W, H, seed=3, sh_degree=deg), P, W, H, deg, mod)
+
+
+@pytest.mark.parametrize("P,W,H,deg,mod", [(2000, 96, 64, 3, 1.0), (3000, 130, 70, 1, 1.4)])
+def test_torch_splat_baseline_matches_oracle_posed(P, W, H, deg, mod):
+    """The same under the steep pose, with capped alphas and a wide SH DC term (posed_cases; no rows
+    past the 1.3 * tanfov clamp: the splat's autograd differentiates through the clamped value, which
+    upstream's backward holds fixed)."""
+    import posed_cases as PC
+    s = PC.populate(O.synthetic_scene(P, W, H, seed=3, sh_degree=deg), 3, opaque=0.2, dark=2.0)
+    _torch_splat_matches_oracle(PC.pose_scene(s, PC.pose("steep", W, H)), P, W, H, deg, mod)
+
+
+def _torch_splat_matches_oracle(s, P, W, H, deg, mod):
     import torch
     import torch_splat as TS
-    s = O.synthetic_scene(P, W, H, seed=3, sh_degree=deg)
     rng = np.random.default_rng(1)
     dcol = (rng.normal(size=(3, H, W)) / (W * H)).astype(np.float32)
     dinv = (rng.normal(size=(1, H, W)) / (W * H)).astype(np.float32)
