@@ -22,10 +22,10 @@
 // workgroup inside a launch:
 //   sort       bounds (block reduce + ordered-uint atomics), keys, rocPRIM pair sort (sort.hip)
 //   topology   one independent thread per interior range (two binary searches over the keys)
-//   numbering  a frontier expansion, one level per step: the level's interior flags counted per
-//              1024-node tile, the tile sums scanned by one workgroup, the node rows written and the
-//              children placed at level_end + 2 rank; the host reads the level's interior count
-//              (one word per level, at most 96 levels)
+//   numbering  a frontier expansion (hier_level.h, shared with hier_merge.hip), one level per step:
+//              the level's interior flags counted per 1024-node tile, the tile sums scanned by one
+//              workgroup, the node rows written and the children placed at level_end + 2 rank; the
+//              host reads the level's interior count (one word per level, at most 96 levels)
 //   merge      the leaves' rows first, then one launch per depth, deepest first.  A level is a
 //              contiguous node range and its children the contiguous range after it, so a launch is
 //              a coalesced sweep with no atomics.  A workgroup takes 256 nodes: a thread per node for
@@ -41,16 +41,13 @@
 #include "../../include/gsr.h"
 #include "../../include/gsr_hier_build.h"
 #include "gsr_launch.h"
+#include "hier_level.h"
 
 namespace gsr {
 namespace {
 
 constexpr int64_t kMaxRows = (int64_t)1 << 30;
-constexpr int kMaxLevels = 96;  // 63 key bits + 32 position bits + the root
 constexpr int kThreads = 256;
-constexpr int kLvlItems = 4, kLvl = kThreads * kLvlItems;  // numbering: nodes per workgroup
-constexpr int kLvlWaves = kThreads / kWave;
-constexpr int kScanThreads = 1024;
 constexpr float kSurfaceP = 1.6075f;
 constexpr float kMinEigen = 1e-14f;
 constexpr int kJacobiSweeps = 8;
@@ -177,129 +174,21 @@ __global__ __launch_bounds__(kThreads) void hb_topology_kernel(int64_t P, const 
 }
 
 // ---- C. layout -----------------------------------------------------------------------------
-// kid[n]: node n's id in the topology (interior j -> j, leaf j -> P - 1 + j).  A level [s, e) is
-// expanded in three launches: the interior nodes per tile, the tile sums' exclusive scan (one
-// workgroup; the level's total to ctl[0]), and the rows of the level with its children's ids,
-// depths and parents at e + 2 rank.
+// The frontier expansion of hier_level.h over Karras's numbering: kid[n] is node n's id in the
+// topology (interior j -> j, leaf j -> P - 1 + j).
 
-__global__ void hb_root_kernel(int *__restrict__ kid, int *__restrict__ nodes) {
-    if (threadIdx.x == 0) {
-        kid[0] = 0;  // interior 0, or the only leaf when P == 1
-        nodes[0] = 0;
-        nodes[1] = -1;
+struct BuildTopo {
+    int64_t P;
+    const int2 *kids;
+    const uint32_t *sorted_row;
+    int *leaf_rows;
+    __device__ __forceinline__ bool interior(int id) const { return (int64_t)id < P - 1; }
+    __device__ __forceinline__ int2 children(int id) const { return kids[id]; }
+    __device__ __forceinline__ void emit(int64_t n, int id, bool inner) const {
+        const int64_t leaf = (int64_t)id - (P - 1);
+        leaf_rows[n] = inner || leaf >= P ? -1 : (int)sorted_row[leaf];
     }
-}
-
-__global__ __launch_bounds__(kThreads) void hb_level_count_kernel(int64_t P, int64_t s, int64_t e,
-                                                                  const int *__restrict__ kid,
-                                                                  uint32_t *__restrict__ tile_sum) {
-    __shared__ uint32_t s_w[kLvlWaves];
-    const int64_t t0 = s + (int64_t)blockIdx.x * kLvl;
-    uint32_t c = 0;
-#pragma unroll
-    for (int k = 0; k < kLvlItems; k++) {
-        const int64_t n = t0 + k * kThreads + threadIdx.x;
-        c += n < e && (int64_t)kid[n] < P - 1 ? 1u : 0u;
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) c += __shfl_xor(c, o, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t tot = 0;
-#pragma unroll
-        for (int k = 0; k < kLvlWaves; k++) tot += s_w[k];
-        tile_sum[blockIdx.x] = tot;
-    }
-}
-
-__global__ __launch_bounds__(kScanThreads) void hb_level_scan_kernel(int64_t ntiles, const uint32_t *__restrict__ tile_sum,
-                                                                     uint64_t *__restrict__ tile_off,
-                                                                     uint64_t *__restrict__ ctl) {
-    __shared__ uint64_t s_w[kScanThreads / kWave];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
-    uint64_t carry = 0;
-    for (int64_t b0 = 0; b0 < ntiles; b0 += kScanThreads) {
-        const int64_t gi = b0 + tid;
-        const uint64_t v = gi < ntiles ? tile_sum[gi] : 0ull;
-        uint64_t inc = v;
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            const uint64_t u = __shfl_up(inc, o, kWave);
-            if (lane >= o) inc += u;
-        }
-        __syncthreads();  // the previous round's reads of s_w are done
-        if (lane == kWave - 1) s_w[w] = inc;
-        __syncthreads();
-        uint64_t before = 0, tot = 0;
-        for (int k = 0; k < kScanThreads / kWave; k++) {
-            before += k < w ? s_w[k] : 0ull;
-            tot += s_w[k];
-        }
-        if (gi < ntiles) tile_off[gi] = carry + before + inc - v;
-        carry += tot;
-    }
-    if (tid == 0) ctl[0] = carry;  // read by the host
-}
-
-__global__ __launch_bounds__(kThreads) void hb_level_write_kernel(int64_t P, int64_t N, int64_t s, int64_t e, int depth,
-                                                                  int *__restrict__ kid, const int2 *__restrict__ kids,
-                                                                  const uint32_t *__restrict__ sorted_row,
-                                                                  const uint64_t *__restrict__ tile_off,
-                                                                  int *__restrict__ nodes, int *__restrict__ leaf_rows) {
-    __shared__ uint32_t s_w[kLvlWaves];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
-    // thread tid holds the tile's nodes kLvlItems tid .. + kLvlItems - 1, in node order
-    const int64_t n0 = s + (int64_t)blockIdx.x * kLvl + (int64_t)kLvlItems * tid;
-    int id[kLvlItems];
-    uint32_t own = 0;
-#pragma unroll
-    for (int k = 0; k < kLvlItems; k++) {
-        id[k] = n0 + k < e ? kid[n0 + k] : INT32_MAX;
-        own += (int64_t)id[k] < P - 1 ? 1u : 0u;
-    }
-    uint32_t incl = own;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, o, kWave);
-        if (lane >= o) incl += t;
-    }
-    if (lane == kWave - 1) s_w[w] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-#pragma unroll
-    for (int k = 0; k < kLvlWaves; k++) before += k < w ? s_w[k] : 0u;
-    uint64_t rank = tile_off[blockIdx.x] + before + incl - own;
-#pragma unroll
-    for (int k = 0; k < kLvlItems; k++) {
-        const int64_t n = n0 + k;
-        if (n >= e) break;
-        const bool interior = (int64_t)id[k] < P - 1;
-        int *row = nodes + 7 * n;  // depth and parent were written with the parent's row
-        row[2] = (int)n;
-        row[3] = interior ? 0 : 1;
-        row[4] = interior ? 1 : 0;
-        int64_t c = -1;
-        if (interior) {
-            c = e + 2 * (int64_t)rank;
-            rank++;
-            if (c + 1 >= N) c = -1;  // cannot happen in a tree of P leaves; nothing is stored past N
-        }
-        row[5] = (int)c;
-        row[6] = c >= 0 ? 2 : 0;
-        int64_t leaf = (int64_t)id[k] - (P - 1);
-        leaf_rows[n] = interior || leaf >= P ? -1 : (int)sorted_row[leaf];
-        if (c >= 0) {
-            const int2 ch = kids[id[k]];
-            kid[c] = ch.x;
-            kid[c + 1] = ch.y;
-            nodes[7 * c] = depth + 1;
-            nodes[7 * c + 1] = (int)n;
-            nodes[7 * (c + 1)] = depth + 1;
-            nodes[7 * (c + 1) + 1] = (int)n;
-        }
-    }
-}
+};
 
 // ---- D, E. attributes ----------------------------------------------------------------------
 
@@ -413,9 +302,7 @@ __device__ __forceinline__ float4 rot_to_quat(const float (&m)[3][3]) {
     return make_float4(r / d, x / d, y / d, z / d);
 }
 
-struct Rows {
-    float *xyz, *ls, *rot, *op, *shs, *boxes;
-};
+using Rows = HierRows;
 
 __device__ __forceinline__ float3 load3(const float *p, int64_t i) {
     return make_float3(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
@@ -465,7 +352,7 @@ __global__ __launch_bounds__(kThreads) void hb_leaf_kernel(int64_t N, int64_t P,
 
 // E: the interior nodes of one level [s, e), their children (rows of the next level) complete.
 __global__ __launch_bounds__(kThreads) void hb_merge_kernel(int64_t N, int64_t s, int64_t e, int M3,
-                                                            const int *__restrict__ nodes, Rows out) {
+                                                            const int *__restrict__ nodes, Rows out, bool abs_opacity) {
     __shared__ int s_child[kThreads];
     __shared__ float2 s_wt[kThreads];
     const int64_t n0 = s + (int64_t)blockIdx.x * kThreads, n = n0 + threadIdx.x;
@@ -479,7 +366,8 @@ __global__ __launch_bounds__(kThreads) void hb_merge_kernel(int64_t N, int64_t s
         float sa[3], sb[3];
         const Sym3 ca = row_cov(load3(out.ls, a), reinterpret_cast<const float4 *>(out.rot)[a], sa);
         const Sym3 cb = row_cov(load3(out.ls, b), reinterpret_cast<const float4 *>(out.rot)[b], sb);
-        const float wa = out.op[a] * surface(sa), wb = out.op[b] * surface(sb);
+        const float oa = abs_opacity ? fabsf(out.op[a]) : out.op[a], ob = abs_opacity ? fabsf(out.op[b]) : out.op[b];
+        const float wa = oa * surface(sa), wb = ob * surface(sb);
         const float W = wa + wb;
         const bool ok = W > 0.f && W <= FLT_MAX;
         const float ua = ok ? wa / W : 0.5f, ub = ok ? wb / W : 0.5f;
@@ -539,7 +427,7 @@ struct BuildScratch {
     void *sort_tmp;
 };
 
-inline int64_t level_tiles(int64_t P) { return (P + kLvl - 1) / kLvl; }  // a level holds at most P nodes
+using hlevel::level_tiles;  // a level holds at most P nodes
 
 size_t build_scratch(int64_t P, size_t sort_bytes, BuildScratch *sc, char *base) {
     size_t at = 0;
@@ -566,8 +454,57 @@ int fail_build(int code, const std::string &m) {
 }
 
 thread_local float t_stage_ms[4] = {0.f, 0.f, 0.f, 0.f};
+thread_local hipEvent_t *t_marks = nullptr;  // gsr_hier_build's own events: [0] after the sort, [1] after the topology
 
 }  // namespace
+
+int hier_build_tree(int64_t P, const float *xyz, int *nodes, int *leaf_rows, std::vector<int64_t> *level_start,
+                    void *scratch, size_t scratch_bytes, hipStream_t s, const char *who) {
+    const auto fail = [&](int code, const std::string &m) {
+        set_last_error(std::string(who) + ": " + m);
+        return code;
+    };
+    const auto dev_fail = [&](const char *what, hipError_t err) {
+        return fail(GSR_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(err));
+    };
+    const size_t sort_bytes = sort_pairs64_temp_bytes((size_t)P, 63);
+    if (scratch_bytes < build_scratch(P, sort_bytes, nullptr, nullptr) + 256)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "scratch too small");
+    BuildScratch sc;
+    (void)build_scratch(P, sort_bytes, &sc, reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(scratch), 256)));
+    int *kid = reinterpret_cast<int *>(sc.key_in);  // N ints in the 2 P ints of the unsorted keys
+    const auto blocks = [](int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); };
+
+    // A. order
+    hipLaunchKernelGGL(hb_init_kernel, dim3(1), dim3(64), 0, s, sc.bb, sc.ctl);
+    const int64_t bounds_blocks = std::min<int64_t>((P + kThreads - 1) / kThreads, 2048);
+    hipLaunchKernelGGL(hb_bounds_kernel, dim3((unsigned)bounds_blocks), dim3(kThreads), 0, s, P, xyz, sc.bb);
+    hipLaunchKernelGGL(hb_keys_kernel, blocks(P, kThreads), dim3(kThreads), 0, s, P, xyz, sc.bb, sc.key_in, sc.row_in);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = sort_pairs64(sc.sort_tmp, sort_bytes, sc.key_in, sc.key, sc.row_in, sc.row, (size_t)P, 63, s);
+    if (e != hipSuccess) return dev_fail("sort", e);
+    if (t_marks) (void)hipEventRecord(t_marks[0], s);
+
+    // B. topology
+    if (P > 1) hipLaunchKernelGGL(hb_topology_kernel, blocks(P - 1, kThreads), dim3(kThreads), 0, s, P, sc.key, sc.kids);
+    if (t_marks) (void)hipEventRecord(t_marks[1], s);
+
+    // C. layout: one level per step; the root is interior 0, or the only leaf when P == 1
+    const BuildTopo topo{P, sc.kids, sc.row, leaf_rows};
+    std::string why;
+    e = hlevel::expand_levels(topo, P, 0, kid, nodes, sc.tile_sum, sc.tile_off, sc.ctl, s, level_start, &why);
+    if (e != hipSuccess) return dev_fail("numbering", e);
+    if (!why.empty()) return fail(GSR_ERR_DEVICE, why);
+    return GSR_OK;
+}
+
+void hier_build_merge_level(int64_t N, int64_t a, int64_t b, int M3, const int *nodes, const HierRows &rows,
+                            bool abs_opacity, hipStream_t s) {
+    if (b <= a) return;
+    hipLaunchKernelGGL(hb_merge_kernel, dim3((unsigned)((b - a + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, N, a, b,
+                       M3, nodes, rows, abs_opacity);
+}
+
 }  // namespace gsr
 
 using namespace gsr;
@@ -604,9 +541,6 @@ int gsr_hier_build(int64_t P, int M, const float *xyz, const float *log_scales, 
         return fail_build(GSR_ERR_INVALID_ARGUMENT, "scratch too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t N = 2 * P - 1;
-    BuildScratch sc;
-    (void)build_scratch(P, sort_bytes, &sc, reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(scratch), 256)));
-    int *kid = reinterpret_cast<int *>(sc.key_in);  // N ints in the 2 P ints of the unsorted keys
     const Rows out{out_xyz, out_log_scales, out_rotations, out_opacities, out_shs, boxes};
     const int M3 = 3 * M;
 
@@ -614,6 +548,7 @@ int gsr_hier_build(int64_t P, int M, const float *xyz, const float *log_scales, 
     hipError_t e = hipSuccess;
     for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
     const auto done = [&](int code, const std::string &m) {
+        t_marks = nullptr;
         for (int k = 0; k < 5; k++)
             if (ev[k]) (void)hipEventDestroy(ev[k]);
         return code == GSR_OK ? GSR_OK : fail_build(code, m);
@@ -624,58 +559,24 @@ int gsr_hier_build(int64_t P, int M, const float *xyz, const float *log_scales, 
     if (e != hipSuccess) return dev_fail("events", e);
     const auto blocks = [](int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); };
 
-    // A. order
+    // A, B, C. order, topology, layout
     (void)hipEventRecord(ev[0], s);
-    hipLaunchKernelGGL(hb_init_kernel, dim3(1), dim3(64), 0, s, sc.bb, sc.ctl);
-    const int64_t bounds_blocks = std::min<int64_t>((P + kThreads - 1) / kThreads, 2048);
-    hipLaunchKernelGGL(hb_bounds_kernel, dim3((unsigned)bounds_blocks), dim3(kThreads), 0, s, P, xyz, sc.bb);
-    hipLaunchKernelGGL(hb_keys_kernel, blocks(P, kThreads), dim3(kThreads), 0, s, P, xyz, sc.bb, sc.key_in, sc.row_in);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = sort_pairs64(sc.sort_tmp, sort_bytes, sc.key_in, sc.key, sc.row_in, sc.row, (size_t)P, 63, s);
-    if (e != hipSuccess) return dev_fail("sort", e);
-    (void)hipEventRecord(ev[1], s);
-
-    // B. topology
-    if (P > 1) hipLaunchKernelGGL(hb_topology_kernel, blocks(P - 1, kThreads), dim3(kThreads), 0, s, P, sc.key, sc.kids);
-    (void)hipEventRecord(ev[2], s);
-
-    // C. layout: one level per step
-    hipLaunchKernelGGL(hb_root_kernel, dim3(1), dim3(64), 0, s, kid, nodes);
     std::vector<int64_t> level_start;
-    int64_t ls = 0, le = 1;
-    for (;;) {
-        if ((int)level_start.size() >= kMaxLevels) return done(GSR_ERR_DEVICE, "more than 96 levels");
-        const int depth = (int)level_start.size();
-        level_start.push_back(ls);
-        const int64_t ntiles = (le - ls + kLvl - 1) / kLvl;
-        hipLaunchKernelGGL(hb_level_count_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, s, P, ls, le, kid, sc.tile_sum);
-        hipLaunchKernelGGL(hb_level_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, ntiles, sc.tile_sum, sc.tile_off, sc.ctl);
-        hipLaunchKernelGGL(hb_level_write_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, s, P, N, ls, le, depth, kid,
-                           sc.kids, sc.row, sc.tile_off, nodes, leaf_rows);
-        e = hipGetLastError();
-        uint64_t interior = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&interior, sc.ctl, sizeof(interior), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return dev_fail("numbering", e);
-        if (interior == 0) break;
-        // a level of a tree of P leaves holds at most P nodes (the tile arrays' size) and ends within N
-        if ((int64_t)interior > (N - le) / 2 || 2 * (int64_t)interior > P)
-            return done(GSR_ERR_DEVICE, "inconsistent topology");
-        ls = le;
-        le += 2 * (int64_t)interior;
+    t_marks = &ev[1];
+    const int rc = hier_build_tree(P, xyz, nodes, leaf_rows, &level_start, scratch, scratch_bytes, s, "gsr_hier_build");
+    if (rc != GSR_OK) {
+        const std::string m = gsr_last_error();
+        (void)done(GSR_OK, "");
+        set_last_error(m);
+        return rc;
     }
-    if (le != N) return done(GSR_ERR_DEVICE, "inconsistent topology");
-    level_start.push_back(N);
     const int L = (int)level_start.size() - 1;
     (void)hipEventRecord(ev[3], s);
 
     // D, E. the leaves, then the interior nodes of each level, deepest first
     hipLaunchKernelGGL(hb_leaf_kernel, blocks(N, kThreads), dim3(kThreads), 0, s, N, P, M3, leaf_rows, xyz, log_scales,
                        rotations, opacities, shs, out);
-    for (int d = L - 2; d >= 0; d--) {
-        const int64_t a = level_start[d], b = level_start[d + 1];
-        hipLaunchKernelGGL(hb_merge_kernel, blocks(b - a, kThreads), dim3(kThreads), 0, s, N, a, b, M3, nodes, out);
-    }
+    for (int d = L - 2; d >= 0; d--) hier_build_merge_level(N, level_start[d], level_start[d + 1], M3, nodes, out, false, s);
     e = hipGetLastError();
     (void)hipEventRecord(ev[4], s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);

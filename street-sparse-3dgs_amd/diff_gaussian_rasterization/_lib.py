@@ -164,6 +164,19 @@ HIER_BUILD_SIGNATURES = {
     "gsr_hier_build_stage_ms": (_i, [ctypes.POINTER(_f), _i]),
 }
 
+# include/gsr_hier_merge.h (the hierarchy merger); typed by load() like SIGNATURES.  New entry points
+# only: the ABI version stays, no existing signature changed
+HIER_MERGE_SIGNATURES = {
+    "gsr_hier_merge_scratch_bytes": (ctypes.c_size_t, [_i64, _i64]),
+    "gsr_hier_merge_top_floats": (ctypes.c_size_t, [_i64, _i]),
+    "gsr_hier_merge_plan": (_i, [_i64, ctypes.POINTER(_i64), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i), _vp, _vp, _vp, _vp, _vp,
+                                 ctypes.c_size_t, _vp]),
+    "gsr_hier_merge_gather": (_i, [_i64, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, ctypes.c_size_t, _vp]),
+    "gsr_hier_merge_stage_ms": (_i, [ctypes.POINTER(_f), _i]),
+}
+
 ABI_VERSION = 7
 _lib = None
 
@@ -186,7 +199,7 @@ def load(path: str = LIB_PATH):
     except OSError as e:  # pragma: no cover - depends on the host
         raise RasterizerLibraryError(f"failed to load {path}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(GT_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
-                              + list(HIER_BUILD_SIGNATURES.items())):
+                              + list(HIER_BUILD_SIGNATURES.items()) + list(HIER_MERGE_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -12,6 +12,7 @@
   synthetic                        seeded synthetic scenes / cameras
   evaluate.Evaluator               test-set PSNR / SSIM / iMAE / iRMSE, whole-image and per region (csrc/eval.hip)
   hier_build.build_hierarchy       a trained chunk's LOD hierarchy (GaussianHierarchyCreator's step; csrc/hier_build.hip)
+  hier_merge.merge_hierarchies     the chunks' hierarchies into the scene's (GaussianHierarchyMerger's step; csrc/hier_merge.hip)
 """
 from .loss import l1_ssim, photo_loss  # noqa: F401
 from .optim import Adam  # noqa: F401

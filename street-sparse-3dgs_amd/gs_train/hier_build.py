@@ -9,8 +9,9 @@ train_post.py (scripts/full_train.py:152,203-216):
 P Gaussians in, N = 2P - 1 nodes out, one Gaussian per node, in the layout expand_to_size,
 get_interpolation_weights, HierarchyModel and write_hierarchy consume.  The rule (DESIGN.md
 "Hierarchy builder") is this project's definition -- Kerbl et al. 2024 sec. 5 over an LBVH -- and is
-parity-unpinned against the un-vendored gaussianhierarchy tool.  Not covered: the chunk merger,
-anchors.bin, the compressed .hier variant, a PLY front end.  There is no CPU path.
+parity-unpinned against the un-vendored gaussianhierarchy tool.  gs_train.hier_merge merges the
+chunks' hierarchies into the scene's.  Not covered: anchors.bin, the compressed .hier variant, a PLY
+front end.  There is no CPU path.
 """
 from __future__ import annotations
 
