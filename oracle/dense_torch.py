@@ -64,7 +64,10 @@ def _mask_fp32(st, pix_x, pix_y, gids):
     return (power <= 0) & (alpha >= np.float32(1.0 / 255.0))
 
 
-def dense_grads(st, dL_dcolor, dL_dinvdepth=None):
+def dense_grads(st, dL_dcolor, dL_dinvdepth=None, per_tile=False):
+    """per_tile: differentiate each tile's share of the loss as soon as it is formed and drop its
+    graph (the gradients are the same sums); a frame of thousands of rows per tile then needs one
+    tile's memory instead of the frame's."""
     dt = torch.float64
     P, W, H = st["P"], st["W"], st["H"]
     V = torch.tensor(st["view"].reshape(4, 4), dtype=dt)
@@ -133,6 +136,9 @@ def dense_grads(st, dL_dcolor, dL_dinvdepth=None):
     gx = (W + 15) // 16
     ranges, plist, ncon = st["ranges"], st["point_list"], st["n_contrib"]
     img_rows, dimg_rows = [], []
+    gcol = torch.tensor(np.asarray(dL_dcolor, np.float64).reshape(3, H, W))
+    with_depth = bool(st["do_depth"]) and dL_dinvdepth is not None
+    gdep = torch.tensor(np.asarray(dL_dinvdepth, np.float64).reshape(H, W)) if with_depth else None
     for tile in range(st["T"]):
         tx0, ty0 = (tile % gx) * 16, (tile // gx) * 16
         xs = np.arange(tx0, min(tx0 + 16, W))
@@ -165,16 +171,23 @@ def dense_grads(st, dL_dcolor, dL_dinvdepth=None):
         w = alpha * Tex
         col = (w @ rgb[g]).T + Tfin[None] * bg[:, None]
         dep = w @ invd[g]
+        if per_tile:
+            loss_t = (col * gcol[:, PY, PX]).sum()
+            if with_depth:
+                loss_t = loss_t + (dep * gdep[PY, PX]).sum()
+            loss_t.backward(retain_graph=True)
+            col, dep = col.detach(), dep.detach()
         img_rows.append((PY, PX, col))
         dimg_rows.append((PY, PX, dep))
     for PY, PX, col in img_rows:
         img = img.index_put((torch.arange(3)[:, None], torch.as_tensor(PY)[None], torch.as_tensor(PX)[None]), col)
     for PY, PX, dep in dimg_rows:
         dimg = dimg.index_put((torch.as_tensor(PY), torch.as_tensor(PX)), dep)
-    loss = (img * torch.tensor(np.asarray(dL_dcolor, np.float64).reshape(3, H, W))).sum()
-    if st["do_depth"] and dL_dinvdepth is not None:
-        loss = loss + (dimg * torch.tensor(np.asarray(dL_dinvdepth, np.float64).reshape(H, W))).sum()
-    loss.backward()
+    if not per_tile:
+        loss = (img * gcol).sum()
+        if with_depth:
+            loss = loss + (dimg * gdep).sum()
+        loss.backward()
     vis = torch.tensor(st["radii"] > 0)
     out = {"color": img.detach().numpy(), "invdepth": dimg.detach().numpy()[None]}
     for k, v in leaves.items():
@@ -182,6 +195,7 @@ def dense_grads(st, dL_dcolor, dL_dinvdepth=None):
         gr = gr * vis.reshape(-1, *([1] * (gr.dim() - 1)))
         out["dL_d" + k] = gr.numpy()
     dm2 = torch.zeros(P, 3, dtype=dt)
-    dm2[:, :2] = ndc.grad * vis[:, None]
+    if ndc.grad is not None:
+        dm2[:, :2] = ndc.grad * vis[:, None]
     out["dL_dmeans2D"] = dm2.numpy()
     return out

@@ -155,10 +155,14 @@ def check_record_offsets(S, vis, K):
         np.testing.assert_array_equal(off[1:], off[:-1] + n[:-1])
 
 
-def compare(c, st, g, h, check_grads=True, global_sort=False, subsets=None):
+def compare(c, st, g, h, check_grads=True, global_sort=False, subsets=None, bars=None):
     """subsets: {name: row mask} (posed_cases.subsets): every gradient tensor is also held to GRAD_TOL
     over the rows of each mask alone, and the SH clamp flags (one byte per row, bit ch set when
-    channel ch clamped at zero: preprocess.hip) equal the oracle's on every row with radii > 0."""
+    channel ch clamped at zero: preprocess.hip) equal the oracle's on every row with radii > 0.
+    bars: {margin name: bar} replacing this file's bar for that margin alone (psnr, nc_bad, frac_off,
+    invdepth_rel_l2, grad_<input>, grad_<input>@<subset>): for cases on which the oracle itself
+    stands further from fp64 than the bar (test_gpu_shapes.py states where its values come from)."""
+    bar = lambda k, default: (bars or {}).get(k, default)
     assert h["K"] == st["K"], f"K {h['K']} vs oracle {st['K']}"
     np.testing.assert_array_equal(h["radii"], st["radii"])
     S = h["state"]
@@ -193,11 +197,11 @@ def compare(c, st, g, h, check_grads=True, global_sort=False, subsets=None):
     inv = rel_l2(h["invdepth"], st["invdepth"]) if c.get("do_depth", True) else None
     margins = dict(psnr=p_img if np.isfinite(p_img) else 999.0, nc_bad=nc_bad, frac_off=off, invdepth_rel_l2=inv)
     try:
-        assert nc_bad <= NC_TOL, f"n_contrib mismatch fraction {nc_bad}"
-        assert p_img >= PSNR_BAR, p_img
-        assert off <= OFF_TOL, off
+        assert nc_bad <= bar("nc_bad", NC_TOL), f"n_contrib mismatch fraction {nc_bad}"
+        assert p_img >= bar("psnr", PSNR_BAR), p_img
+        assert off <= bar("frac_off", OFF_TOL), off
         if inv is not None:
-            assert inv <= INV_TOL, inv
+            assert inv <= bar("invdepth_rel_l2", INV_TOL), inv
         if not check_grads:
             return
         G = h["grads"]
@@ -213,11 +217,12 @@ def compare(c, st, g, h, check_grads=True, global_sort=False, subsets=None):
         for hk, ok in pairs:
             err = rel_l2(G[hk].reshape(g[ok].shape), g[ok])
             margins["grad_" + hk] = err
-            assert err <= GRAD_TOL, f"{c['name']}: grad {hk} rel L2 {err}"
+            assert err <= bar("grad_" + hk, GRAD_TOL), f"{c['name']}: grad {hk} rel L2 {err}"
             for name, m in (subsets or {}).items():
                 err = rel_l2(G[hk].reshape(g[ok].shape)[m], g[ok][m])
                 margins[f"grad_{hk}@{name}"] = err
-                assert err <= GRAD_TOL, f"{c['name']}: grad {hk} over the {int(m.sum())} {name} rows rel L2 {err}"
+                assert err <= bar(f"grad_{hk}@{name}", GRAD_TOL), \
+                    f"{c['name']}: grad {hk} over the {int(m.sum())} {name} rows rel L2 {err}"
     finally:
         record_margins(c["name"], **margins)
     return
