@@ -999,18 +999,17 @@ bool bwd_zero_rows(const GaussianInputs &in, const GaussianGrads &out, const Bwd
     return true;
 }
 
-void launch_preprocess_bwd(const GaussianInputs &in, const Camera &cam, const GeomState &gs, const ImageState &is,
+bool launch_preprocess_bwd(const GaussianInputs &in, const Camera &cam, const GeomState &gs, const ImageState &is,
                            const int *radii, const BwdScratch &sc, const GaussianGrads &out, hipStream_t s,
-                           const ZeroRows *zr) {
+                           const ZeroRows *zr, const StepAct *step_act) {
     const bool rows_zeroed = zr != nullptr;
-    if (in.P == 0) return;
+    if (in.P == 0) return false;
     if (!sc.atomic)  // atomic mode: the sums are already in sc.acc
         hipLaunchKernelGGL(record_sum_kernel, dim3((in.P + 255) / 256), dim3(256), 0, s, in.P, cam.gx, in.means3D,
                        cam.view, gs.rect8, gs.rect4, gs.offsets, is.boundary, sc, out.dmeans2D, out.dopacity);
     const bool split = split_ok(in, out, sc);
-    note_step_act_done(false);
     // the native step's fused activation backward needs the raw parameters (GaussianInputs.raw)
-    StepAct act = step_act();
+    StepAct act = step_act ? *step_act : StepAct{};
     if (!in.raw || !out.sparse_rows) act.on = 0;
     if (split) {
         // rows zeroed by render_bwd: its stamps name the live rows (no grad_rows pass); otherwise
@@ -1033,14 +1032,14 @@ void launch_preprocess_bwd(const GaussianInputs &in, const Camera &cam, const Ge
                                in.scales, in.rotations, in.scale_modifier, la.dscale_mod, cam.view, cam.proj,
                                cam.campos, cam.tanx, cam.tany, cam.fx, cam.fy, sc, out, in.raw, stamps, stamp, act);
         }
-        note_step_act_done(act.on != 0);
-        return;
+        return act.on != 0;
     }
     hipLaunchKernelGGL(preprocess_bwd_kernel, dim3((in.P + 255) / 256), dim3(256), 0, s, in.P, in.D, in.M, in.means3D,
                        radii, in.shs, gs.clamped, in.scales, in.rotations, in.scale_modifier,
                        true_scale_gradient() ? in.scale_modifier : 1.0f, in.cov3D_precomp,
                        cam.view, cam.proj, cam.campos, cam.tanx, cam.tany, cam.fx, cam.fy, cam.gx, gs.tiles, gs.rec,
                        is.boundary, sc, out, in.raw);
+    return false;
 }
 
 GSR_KSTAMP_READER(kstamp_read_backward)

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include "gsr_device.h"
+#include "../../include/gsr.h"
 #include "../../include/gsr_train.h"
 
 namespace gsr {
@@ -21,7 +22,7 @@ struct Camera {
     int W, H, gx, gy;
 };
 
-// raw (the native train step, set_raw_params): scales / rotations / opacities are the
+// raw (the native train step, FrameOpts / BackwardOpts): scales / rotations / opacities are the
 // pre-activation parameters (log-scales, unnormalised quaternions, logits), activated in the
 // kernels that read them (gsr_device.h act_*), so no activated copy is written and re-read.
 struct GaussianInputs {
@@ -35,9 +36,6 @@ struct GaussianInputs {
 };
 // the fused cut is supported for SH frames the colour pass takes (M = 16), scales + rotations
 bool cut_fusable(const GaussianInputs &in);
-// rasterizer.hip: gsr_rasterize_forward_ex / gsr_rasterize_backward on this thread take raw
-// parameters (plain frames: no precomputed covariance, no hierarchy cut)
-void set_raw_params(bool on);
 
 // preprocess.hip
 void launch_preprocess(const GaussianInputs &in, const Camera &cam, const GeomState &gs, int *radii,
@@ -109,7 +107,7 @@ uint32_t *dsort_aux_word(const GeomState &gs);
 uint32_t *dsort_maxsb_word(const GeomState &gs);
 // the forward split's queue-ready word (zeroed with the control words by every frame's preprocess)
 uint32_t *dsort_fwdready_word(const GeomState &gs);
-int device_cus();  // compute units of the current device (rasterizer.hip, cached)
+int device_cus();  // compute units of the current device (rasterizer.hip, cached per device)
 uint32_t *dsort_live_words(const GeomState &gs);
 uint32_t *dsort_culled_word(const GeomState &gs);  // culled Gaussians of the frame (the upsweep's sum)
 int dsort_head_words();
@@ -178,7 +176,7 @@ uint32_t fseg_min_len(uint32_t Lf);  // the shortest list the forward split take
 uint32_t set_fwd_split_min(uint32_t len);  // gsr_set_fwd_split_min
 
 // backward.hip
-// sparse_rows (the native train step only, set_sparse_grad_rows): the rows of Gaussians with ten
+// sparse_rows (the native train step only, BackwardOpts): the rows of Gaussians with ten
 // zero accumulated sums (every gradient zero) are not written in dmeans3D / dsh / dscales / drots,
 // and dmeans2D's third column carries the row's liveness (1 written, 0 not) instead of its zero.
 // Only rows whose opacity gradient is nonzero are read by the sparse Adam (OurAdam's `relevant`,
@@ -187,16 +185,15 @@ struct GaussianGrads {
     float *dmeans2D, *dcolors, *dopacity, *dmeans3D, *dcov3D, *dsh, *dscales, *drots;
     int sparse_rows;
 };
-// rasterizer.hip: gsr_rasterize_backward on this thread writes sparse rows (see above)
-void set_sparse_grad_rows(bool on);
 
 // The native step's activation backward fused into the live-row pass of preprocess_bwd
-// (set_step_act around gsr_rasterize_backward): the gradient outputs are then the raw parameters'
+// (BackwardOpts.act): the gradient outputs are then the raw parameters'
 // gradients (dscales / drots / dopacity: of the log-scales, the unnormalised quaternions and the
 // logits, skybox rows' opacity gradient locked at zero, train_single.py:217-223), the
 // densification statistics of every visible row are updated (train_single.py:193-194) and *flag
-// is set when a row's opacity gradient is nonzero (OurAdam's `relevant`).  step_act_done() says
-// whether the last backward on this thread did it (else the caller runs the activation backward).
+// is set when a row's opacity gradient is nonzero (OurAdam's `relevant`).  launch_preprocess_bwd
+// returns whether it did it (else the caller runs the activation backward): only with raw inputs
+// and sparse rows, and only on the split path.
 struct StepAct {
     const float *s_raw, *o_raw;
     const float4 *q_raw;
@@ -206,18 +203,29 @@ struct StepAct {
     int *flag;
     int on;
 };
-void set_step_act(const StepAct *a);
-StepAct step_act();
 bool live_list();  // gsr_set_live_list
-void note_step_act_done(bool done);
-bool step_act_done();
-void launch_preprocess_bwd(const GaussianInputs &in, const Camera &cam, const GeomState &gs, const ImageState &is,
+bool launch_preprocess_bwd(const GaussianInputs &in, const Camera &cam, const GeomState &gs, const ImageState &is,
                            const int *radii, const BwdScratch &sc, const GaussianGrads &out, hipStream_t s,
-                           const ZeroRows *zr = nullptr);
+                           const ZeroRows *zr = nullptr, const StepAct *step_act = nullptr);
 // the frame's gradient arrays for render_bwd to zero and its live stamps (false: preprocess_bwd
 // writes the zeros itself -- record mode, the single-kernel path or unaligned arrays)
 bool bwd_zero_rows(const GaussianInputs &in, const GaussianGrads &out, const BwdScratch &sc, uint32_t *gs_stamps,
                    int nblocks, ZeroRows *z);
+
+// rasterizer.hip: the bodies of gsr_rasterize_forward_ex / gsr_rasterize_backward: run() takes the
+// C entry point's arguments (include/gsr.h; same checks and errors), the members are the options
+// only the native train step sets -- the C entry points run them with the defaults.
+// raw_params: plain frames only (no precomputed covariance, no hierarchy cut).
+struct ForwardCall {
+    bool raw_params = false;  // GaussianInputs.raw
+    decltype(gsr_rasterize_forward_ex) run;
+};
+struct BackwardCall {
+    bool raw_params = false, sparse_rows = false;  // GaussianInputs.raw, GaussianGrads.sparse_rows
+    const StepAct *act = nullptr;                  // NULL: none
+    bool act_done = false;                         // out: run() did the fused activation backward
+    decltype(gsr_rasterize_backward) run;
+};
 
 // train.hip: the native train step's fused launches (train_step.hip).  sparse_adam is
 // gsr_sparse_adam_step (flag_ready: the relevance flag is already computed; shrink_raw != NULL:

@@ -22,30 +22,13 @@
 
 using namespace gsr;
 
-namespace gsr {
-// compute units of the current device (cached per device)
-int device_cus() {
-    static int cache[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cache[dev]) {
-        int n = 0;
-        cache[dev] = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
-    }
-    return cache[dev];
-}
-}  // namespace gsr
-
 namespace {
 
 thread_local std::string g_err;
-// K (num_rendered) arrives in pinned, host-coherent memory written by the depth sort's first
-// kernel; the host waits on an event recorded right after it, so the sort passes keep running
-// while the host sizes the binning buffer.
-// g_pinned[kHostK] = K, [kHostErr] = sticky depth-sort error (a lookback spin gave up; never
-// expected), [kHostMaxSB] / [kHostP1] = a local-sort frame's longest SB list / level-1 total
-thread_local uint32_t *g_pinned = nullptr;
-thread_local uint32_t *g_pinned_dev = nullptr;
+int fail(int code, const std::string &msg) {
+    g_err = msg;
+    return code;
+}
 // forward statistics (gsr_forward_stats): frames, binning re-runs at K (capacity hint short)
 std::atomic<int64_t> g_frames{0}, g_reruns{0}, g_local_frames{0}, g_fallbacks{0};
 // binning mode (gsr_set_binning): 0 = local sort where it applies, 1 = always the global depth sort.
@@ -56,13 +39,23 @@ std::atomic<int64_t> g_frames{0}, g_reruns{0}, g_local_frames{0}, g_fallbacks{0}
 #define GSR_BINNING_DEFAULT 1
 #endif
 std::atomic<int> g_binning_mode{GSR_BINNING_DEFAULT};
-// the native train step's sparse gradient rows (gsr_launch.h GaussianGrads), per calling thread
-thread_local bool g_sparse_grad_rows = false;
-thread_local bool g_raw_params = false;  // GaussianInputs.raw, per calling thread
-thread_local gsr::StepAct g_step_act{};    // set_step_act
-std::atomic<int> g_live_list{0};           // gsr_set_live_list
-thread_local bool g_step_act_done = false;
-constexpr int kMaxDevicesK = 64;
+std::atomic<int> g_live_list{0};  // gsr_set_live_list
+std::atomic<int> g_split_gate{1};  // gsr_set_split_gate
+
+// A side stream for work that overlaps the main stream's latency-bound stages (the SH colour pass
+// runs beside the depth sort and the binning); fork / join with events, so it also works inside a
+// captured HIP graph.
+struct Side {
+    hipStream_t st = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    // the side stream waits for what s holds now
+    bool fork_from(hipStream_t s) const {
+        return hipEventRecord(fork, s) == hipSuccess && hipStreamWaitEvent(st, fork, 0) == hipSuccess;
+    }
+    bool record_join() const { return hipEventRecord(join, st) == hipSuccess; }
+    bool join_into(hipStream_t s) const { return hipStreamWaitEvent(s, join, 0) == hipSuccess; }
+};
+
 // The backward's per-Gaussian accumulator rows (64 B each: render_bwd's ten float-atomic sums):
 // one grow-only array per device, all zero between backwards --
 // render_bwd adds into the rows of the Gaussians it reaches and the consumer (preprocess_bwd or
@@ -77,15 +70,60 @@ struct AccRows {
     bool dirty = false;
     hipStream_t last = nullptr;  // the stream of the last backward that used the rows
 };
-std::mutex g_acc_mu;
-AccRows g_acc_rows[kMaxDevicesK];
-// The device's rows for a backward of n rows on stream s (stream-ordered growth and clears); marked
-// dirty until acc_rows_consumed() -- the backward has queued the consumer.  NULL on failure.
-float4 *acc_rows(hipStream_t s, size_t n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesK) return nullptr;
-    std::lock_guard<std::mutex> lk(g_acc_mu);
-    AccRows &a = g_acc_rows[dev];
+
+// What the process keeps per device.  A forward / backward call looks its thread's current device
+// up once (current_device) and hands the record down.
+constexpr int kMaxDevices = 64;
+constexpr int kSides = 2;  // 0: the colour pass and the forward segments' workers; 1: the tile_bin split
+struct Device {
+    std::mutex acc_mu;  // held by an AccLease
+    AccRows acc;
+    std::mutex mu;  // the side streams, created on first use
+    Side sides[kSides];
+    std::atomic<int> cus{0};  // compute units
+
+    bool side(int which, Side *out) {
+        std::lock_guard<std::mutex> lk(mu);
+        Side &sd = sides[which];
+        if (!sd.st) {
+            if (hipStreamCreateWithFlags(&sd.st, hipStreamNonBlocking) != hipSuccess) return false;
+            if (hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming) != hipSuccess ||
+                hipEventCreateWithFlags(&sd.join, hipEventDisableTiming) != hipSuccess)
+                return false;
+        }
+        *out = sd;
+        return true;
+    }
+} g_devices[kMaxDevices];
+Device *current_device() {  // NULL: none, or one past kMaxDevices
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
+    Device &d = g_devices[dev];
+    if (!d.cus.load(std::memory_order_relaxed))
+        d.cus = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+    return &d;
+}
+
+// The device's rows leased to one backward, from the hand-out (rows) until it has queued their
+// consumer (consumed): the lease holds the device's lock over that span, so backwards from several
+// host threads neither add into the same rows at once nor free a block another is about to launch
+// on.  Every other exit leaves the rows dirty; the destructor unlocks.
+struct AccLease {
+    Device *d;
+    std::unique_lock<std::mutex> lk;
+    explicit AccLease(Device *dev) : d(dev) {
+        if (d) lk = std::unique_lock<std::mutex>(d->acc_mu);
+    }
+    float4 *rows(hipStream_t s, size_t n);
+    void consumed() {
+        d->acc.dirty = false;
+        lk.unlock();
+    }
+};
+// for a backward of n rows on stream s (stream-ordered growth and clears); NULL on failure
+float4 *AccLease::rows(hipStream_t s, size_t n) {
+    if (!d) return nullptr;
+    AccRows &a = d->acc;
     // another stream's backward may still be adding into / consuming the rows (a stream may since
     // have been destroyed, so the whole device is waited for; backwards on one stream need nothing)
     if (a.last && a.last != s && hipDeviceSynchronize() != hipSuccess) return nullptr;
@@ -108,31 +146,75 @@ float4 *acc_rows(hipStream_t s, size_t n) {
     a.last = s;
     return a.p;
 }
-void acc_rows_consumed() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesK) return;
-    std::lock_guard<std::mutex> lk(g_acc_mu);
-    g_acc_rows[dev].dirty = false;
-}
-thread_local hipEvent_t g_k_ready[kMaxDevicesK] = {};
-// per device: capacity for the next frame's point list, 0 = none yet.  It is the largest K of the
-// last kKHist (256) frames + 1/8 + 4096, so a training loop cycling its cameras (whose K differs from
-// view to view) rarely comes up short and re-runs the binning (gsr_forward_stats counts re-runs).
+
 constexpr int kKHist = 256;
-thread_local int64_t g_khint[kMaxDevicesK] = {};
-thread_local int64_t g_khist[kMaxDevicesK][kKHist] = {};
-thread_local int g_khead[kMaxDevicesK] = {};
 constexpr uint32_t kKPending = 0xFFFFFFFFu;
-// The split gate (gsr_set_split_gate): the forward split and the tile_bin split cost launches and
-// stream hand-offs on every frame they are armed for, and pay only on frames with very long lists
-// (a street view after an opacity reset), so they are armed for kSplitMemory frames after a frame
-// (per device and thread) whose longest tile / superblock list called for them -- the kernels report
-// those lengths in pinned memory, read at the next forward.
 constexpr int64_t kSplitMemory = 256;
-thread_local int64_t g_frame_no[kMaxDevicesK] = {};
-thread_local int64_t g_long_tile_at[kMaxDevicesK] = {};
-thread_local int64_t g_long_sb_at[kMaxDevicesK] = {};
-std::atomic<int> g_split_gate{1};
+// What a host thread keeps per device it has run a forward on (pinned == NULL: none yet).
+struct ThreadDevice {
+    // K (num_rendered) arrives in pinned, host-coherent memory written by the depth sort's first
+    // kernel; the host waits on an event recorded right after it (k_ready), so the sort passes keep
+    // running while the host sizes the binning buffer.
+    // pinned[kHostK] = K, [kHostErr] = sticky depth-sort error (a lookback spin gave up; never
+    // expected), [kHostMaxSB] / [kHostP1] = a local-sort frame's longest SB list / level-1 total
+    uint32_t *pinned = nullptr, *pinned_dev = nullptr;
+    hipEvent_t k_ready = nullptr;
+    // capacity for the next frame's point list, 0 = none yet.  It is the largest K of the last
+    // kKHist (256) frames + 1/8 + 4096, so a training loop cycling its cameras (whose K differs from
+    // view to view) rarely comes up short and re-runs the binning (gsr_forward_stats counts re-runs).
+    int64_t khint = 0, khist[kKHist] = {};
+    int khead = 0;
+    // The split gate (gsr_set_split_gate): the forward split and the tile_bin split cost launches and
+    // stream hand-offs on every frame they are armed for, and pay only on frames with very long lists
+    // (a street view after an opacity reset), so they are armed for kSplitMemory frames after a frame
+    // whose longest tile / superblock list called for them -- the kernels report those lengths in
+    // the pinned words, read at the next forward.
+    int64_t frame_no = 0, long_tile_at = 0, long_sb_at = 0;
+
+    int ensure() {
+        if (!pinned) {
+            if (hipHostMalloc(reinterpret_cast<void **>(&pinned), kHostWords * sizeof(uint32_t),
+                              hipHostMallocCoherent) != hipSuccess ||
+                hipHostGetDevicePointer(reinterpret_cast<void **>(&pinned_dev), pinned, 0) != hipSuccess)
+                return fail(GSR_ERR_ALLOCATION, "pinned host allocation failed");
+            for (int k = 0; k < kHostWords; k++) pinned[k] = 0u;
+            long_tile_at = long_sb_at = -2 * kSplitMemory;
+        }
+        if (!k_ready && hipEventCreateWithFlags(&k_ready, hipEventDisableTiming) != hipSuccess)
+            return fail(GSR_ERR_DEVICE, "event creation failed");
+        return GSR_OK;
+    }
+    // the gate on this frame's requested splits: the longest lists of the frames before (whatever
+    // the pinned words hold now) arm them
+    void split_gate(uint32_t fseg_min, uint32_t *fseg_req, uint32_t *tb_req) {
+        const int64_t f = ++frame_no;
+        const uint32_t tl = __atomic_load_n(&pinned[kHostTileList], __ATOMIC_RELAXED);
+        const uint32_t sl = __atomic_load_n(&pinned[kHostSBList], __ATOMIC_RELAXED);
+        if (*fseg_req && tl > fseg_min) long_tile_at = f;
+        if (*tb_req && sl > *tb_req) long_sb_at = f;
+        if (g_split_gate.load(std::memory_order_relaxed)) {
+            if (f - long_tile_at > kSplitMemory) *fseg_req = 0;
+            if (f - long_sb_at > kSplitMemory) *tb_req = 0;
+        }
+    }
+    void note_K(int64_t K) {
+        khist[khead] = K;
+        khead = (khead + 1) % kKHist;
+        int64_t kmax = 0;
+        for (int i = 0; i < kKHist; i++) kmax = std::max(kmax, khist[i]);
+        // the kernels compare K with a 32-bit capacity: keep the hint representable
+        khint = std::min<int64_t>(kmax + kmax / 8 + 4096, (int64_t)UINT32_MAX);
+    }
+    void reset() {  // gsr_reset_capacity_hint
+        if (pinned) pinned[kHostTileList] = pinned[kHostSBList] = 0u;
+        long_tile_at = long_sb_at = frame_no - 2 * kSplitMemory;
+        khint = 0;
+        khead = 0;
+        for (int i = 0; i < kKHist; i++) khist[i] = 0;
+    }
+};
+thread_local ThreadDevice t_devices[kMaxDevices];
+ThreadDevice &thread_device(const Device *d) { return t_devices[d - g_devices]; }
 
 // Stage profiling is process-wide: torch runs the backward on its autograd device thread.
 constexpr int kStages = 10;
@@ -142,46 +224,6 @@ bool g_ev_init = false;
 hipEvent_t g_ev_begin[kStages], g_ev_end[kStages];
 bool g_ev_recorded[kStages];
 
-// Side stream for work that overlaps the main stream's latency-bound stages (the SH colour
-// pass runs beside the depth sort and the binning); fork / join with events, so it also works
-// inside a captured HIP graph.  One per device, created on first use.
-constexpr int kMaxDevices = 64;
-std::mutex g_side_mu;
-constexpr int kSides = 2;  // 0: the colour pass and the forward segments' workers; 1: the tile_bin split
-hipStream_t g_side[kSides][kMaxDevices] = {};
-hipEvent_t g_fork[kSides][kMaxDevices] = {}, g_join[kSides][kMaxDevices] = {};
-
-bool side_stream(hipStream_t *side, hipEvent_t *fork, hipEvent_t *join, int which = 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
-    std::lock_guard<std::mutex> lk(g_side_mu);
-    if (!g_side[which][dev]) {
-        if (hipStreamCreateWithFlags(&g_side[which][dev], hipStreamNonBlocking) != hipSuccess) return false;
-        if (hipEventCreateWithFlags(&g_fork[which][dev], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&g_join[which][dev], hipEventDisableTiming) != hipSuccess)
-            return false;
-    }
-    *side = g_side[which][dev];
-    *fork = g_fork[which][dev];
-    *join = g_join[which][dev];
-    return true;
-}
-
-// Joins the side stream into the main one when the forward leaves early (errors), so the
-// caller's buffers are never released under side-stream work.
-struct SideJoin {
-    hipStream_t s = nullptr;
-    hipEvent_t join = nullptr;
-    bool pending = false;
-    ~SideJoin() {
-        if (pending) (void)hipStreamWaitEvent(s, join, 0);
-    }
-};
-
-int fail(int code, const std::string &msg) {
-    g_err = msg;
-    return code;
-}
 
 // A lookback timeout of this or an earlier frame's depth sort (the pass kernels store the pinned
 // word; its frame's render_fwd already wrote NaN pixels): fail this call, once per occurrence.
@@ -196,19 +238,22 @@ std::atomic<int64_t> g_fsplit_frames{0}, g_tbsplit_frames{0};
 // completed by a sort pass queued after K was read (none: every frame queues its four launches)
 std::atomic<int64_t> g_sort_wide_frames{0}, g_sort_late_pass{0};
 constexpr int kFwdStats = 10;
-void collect_giveups() {
-    if (!g_pinned) return;
-    const uint32_t gu = __atomic_exchange_n(&g_pinned[kHostFwdGiveUp], 0u, __ATOMIC_SEQ_CST);
+// (both read the calling thread's pinned words for device d; no record: nothing to report)
+void collect_giveups(const Device *d) {
+    uint32_t *const pinned = d ? thread_device(d).pinned : nullptr;
+    if (!pinned) return;
+    const uint32_t gu = __atomic_exchange_n(&pinned[kHostFwdGiveUp], 0u, __ATOMIC_SEQ_CST);
     if (gu && g_fwd_giveups.fetch_add(1) == 0)
         fprintf(stderr, "[gsr] forward split: workers gave up waiting for tile_order (side and main streams not "
                         "concurrent); the frame was completed by the pool's second launch, slower "
                         "(gsr_forward_stats[4] counts such frames)\n");
 }
-int sticky_sort_error() {
-    if (!g_pinned) return GSR_OK;
-    collect_giveups();
-    const uint32_t e = __atomic_exchange_n(&g_pinned[kHostErr], 0u, __ATOMIC_SEQ_CST);
-    const uint32_t fe = __atomic_exchange_n(&g_pinned[kHostFwdErr], 0u, __ATOMIC_SEQ_CST);
+int sticky_sort_error(const Device *d) {
+    uint32_t *const pinned = d ? thread_device(d).pinned : nullptr;
+    if (!pinned) return GSR_OK;
+    collect_giveups(d);
+    const uint32_t e = __atomic_exchange_n(&pinned[kHostErr], 0u, __ATOMIC_SEQ_CST);
+    const uint32_t fe = __atomic_exchange_n(&pinned[kHostFwdErr], 0u, __ATOMIC_SEQ_CST);
     if (e) return fail(GSR_ERR_DEVICE, "depth sort: a lookback spin timed out (this or an earlier frame; its image is NaN)");
     if (fe)
         return fail(GSR_ERR_DEVICE, "forward split: a worker's wait for a predecessor segment timed out (this or an "
@@ -367,7 +412,7 @@ ImageState carve_image(void *base, int T, int npix, size_t *bytes) {
     return s;
 }
 
-// atomic mode needs no record scratch (the accumulators are the device's persistent rows, acc_rows)
+// atomic mode needs no record scratch (the accumulators are the device's persistent rows, AccRows)
 BwdScratch carve_bwd(void *base, int64_t K, int P, bool atomic, size_t *bytes, bool list) {
     Carver c(base);
     BwdScratch s{};
@@ -484,13 +529,11 @@ std::atomic<int> g_true_scale_grad{0};
 std::atomic<int> g_deterministic{GSR_DETERMINISTIC_DEFAULT};
 }
 bool gsr::true_scale_gradient() { return g_true_scale_grad.load(std::memory_order_relaxed) != 0; }
-void gsr::set_sparse_grad_rows(bool on) { g_sparse_grad_rows = on; }
-void gsr::set_raw_params(bool on) { g_raw_params = on; }
-void gsr::set_step_act(const StepAct *a) { g_step_act = a ? *a : StepAct{}; }
 bool gsr::live_list() { return g_live_list.load(std::memory_order_relaxed) != 0; }
-gsr::StepAct gsr::step_act() { return g_step_act; }
-void gsr::note_step_act_done(bool done) { g_step_act_done = done; }
-bool gsr::step_act_done() { return g_step_act_done; }
+int gsr::device_cus() {
+    Device *d = current_device();
+    return d ? d->cus.load() : 256;
+}
 
 namespace {
 // Geometry buffers of forwards no atomic-mode backward may follow ("uncleared": until round 6 the
@@ -551,6 +594,551 @@ uint32_t forward_seg(const void *image) {
     return it == g_seg_of.end() ? g_bwd_seg.load(std::memory_order_relaxed) : it->second;
 }
 }  // namespace
+
+namespace {
+#ifndef GSR_COLOR_LOCAL_BLOCKS
+#define GSR_COLOR_LOCAL_BLOCKS 128  // local-sort frames: the colour pass's persistent grid beside the binning
+#endif
+// Where the SH colour pass forks (early: right after the preprocess, else after the sort) and as
+// how many blocks (0: a full grid of 8-wave blocks).
+// The depth sort runs one 1024-thread workgroup per 8192 keys (dsort_blocks) and leaves the
+// other CUs idle: when it leaves a good share of them, the SH colour pass forks right after the
+// preprocess as a persistent grid on those CUs (1M Gaussians: 123 sort workgroups, 128 colour
+// blocks; 2640 -> 2696 Mpix/s, 133 blocks already slowed the sort); otherwise it forks after the sort, beside the
+// binning, at full width.  Local-sort frames fork it right after the preprocess too, as a
+// persistent grid of GSR_COLOR_LOCAL_BLOCKS blocks beside the binning.
+struct ColorPlan { bool early; int blocks; };
+ColorPlan color_plan(int P, bool local, bool split, Device *dev) {
+    if (!split) return {false, 0};
+    if (local) return {true, GSR_COLOR_LOCAL_BLOCKS};
+    // workgroups are dealt round-robin over the 8 XCDs: leave every XCD room for its share
+    // of the sort's workgroups (123 of them -> 16 per XCD -> 8 x (32 - 16) = 128 colour blocks)
+    const int per_xcd = dev->cus / 8;
+    const int free_cus = 8 * (per_xcd - (dsort_blocks(P) + 7) / 8);
+    if (free_cus >= 2 * per_xcd) return {true, free_cus};
+    // the sort fills the chip (large P).  Two rounds of it or more (config 5's 7.46M rows):
+    // the colour pass forks right after the preprocess, so it overlaps the sort as well
+    // as the binning (config 5 3.62 -> 3.51 ms, r05f); config 3's 3M-row frames measured
+    // no gain (55.0 vs 55.3 s), so they keep the fork after the sort.  Either way a full
+    // grid of 8-wave blocks.
+    return {dsort_blocks(P) >= 2 * dev->cus, 0};
+}
+
+// One forward call: what its stages share.
+struct Frame {
+    hipStream_t s;  // of the call's arguments
+    int debug;
+    bool need_bwd;
+    const float *background;
+    float *out_color, *out_invdepth;
+    gsr_resize_fn binning_buffer;
+    void *resize_ctx;
+    GaussianInputs in;
+    Camera cam;
+    int T;
+    GeomState gs;
+    ImageState is;
+    Device *dev;
+    ThreadDevice *td;
+    // the SH colour pass on the side stream, beside the sort and / or the binning; join_pending:
+    // forked and not yet joined into s
+    bool join_pending;
+    Side color;
+    int color_blocks;
+    bool local, have_K;
+    hipEvent_t k_ready;
+    int64_t K;
+    uint32_t maxsb, seg_req, fseg_req, tb_req, fseg_min, seg_used;
+    FwdSpin spin;
+    bool fsplit_armed, tbsplit_armed;
+
+    int fork_color(const int *vis_radii);
+    int read_K();
+    int to_global();
+    int bin_and_render(int64_t cap, bool counted);
+    // joins the side stream into the main one when the forward leaves early (errors), so the
+    // caller's buffers are never released under side-stream work
+    ~Frame() {
+        if (join_pending) (void)hipStreamWaitEvent(s, color.join, 0);
+    }
+};
+
+// fork: the SH colours stream in beside latency-bound main-stream stages; joined before render_fwd
+int Frame::fork_color(const int *vis_radii) {
+    if (!color.fork_from(s)) return fail(GSR_ERR_DEVICE, "side stream fork failed");
+    {
+        StageTimer st(8, color.st);
+        launch_preprocess_color(in, cam, gs, vis_radii, color.st, color_blocks);
+    }
+    if (!color.record_join()) return fail(GSR_ERR_DEVICE, "side stream join record failed");
+    join_pending = true;
+    return check("preprocess colour", debug, color.st);
+}
+
+// waits for K (and a local frame's longest SB list)
+int Frame::read_K() {
+    uint32_t *const pinned = td->pinned;
+    const auto t_wait = std::chrono::steady_clock::now();
+    if (k_ready) {
+        if (hipEventSynchronize(k_ready) != hipSuccess) return fail(GSR_ERR_DEVICE, "num_rendered wait failed");
+    } else {
+        // the frame is queued; the upsweep's (column scan's) last workgroup stores K into the
+        // pinned word (it is normally there already: the host runs ahead of the GPU).  A drained
+        // stream with the word still pending falls through to the device copy below.
+        while (__atomic_load_n(&pinned[kHostK], __ATOMIC_SEQ_CST) == kKPending) {
+            const hipError_t q = hipStreamQuery(s);
+            if (q == hipSuccess) break;
+            if (q != hipErrorNotReady) return fail(GSR_ERR_DEVICE, "num_rendered wait failed");
+            std::this_thread::yield();
+        }
+    }
+    g_kwait_ns.fetch_add(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() -
+                                                                               t_wait).count(),
+                         std::memory_order_relaxed);
+    uint32_t k = __atomic_load_n(&pinned[kHostK], __ATOMIC_ACQUIRE);
+    uint32_t m = __atomic_load_n(&pinned[kHostMaxSB], __ATOMIC_ACQUIRE);
+    if (k == kKPending) {  // not expected: read the device copies instead (a local frame's K
+                           // word may read "capacity short": its instance total is K)
+        const uint32_t *kw = local ? gs.sb_base_i + gs.sb.nsb : dsort_K_word(gs);
+        if (hipMemcpy(&k, kw, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(&m, dsort_maxsb_word(gs), sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(GSR_ERR_DEVICE, "num_rendered copy failed");
+    }
+    if (debug && !local) {  // the sort passes are complete here (debug syncs after every stage)
+        uint32_t err = 0;
+        if (hipMemcpy(&err, dsort_err_word(gs), sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess || err)
+            return fail(GSR_ERR_DEVICE, "depth sort: a lookback spin timed out");
+    }
+    if (int rc = sticky_sort_error(dev)) return rc;
+    // stored before K by the upsweep (0 on a local-sort frame and when K came from the device copy)
+    if (__atomic_load_n(&pinned[kHostWide], __ATOMIC_RELAXED))
+        g_sort_wide_frames.fetch_add(1, std::memory_order_relaxed);
+    K = (int64_t)k;
+    maxsb = local ? m : 0u;
+    have_K = true;
+    return GSR_OK;
+}
+
+// a local frame re-run through the global sort: the head control words (tickets, counters, K)
+// start from zero again, the lookback status words are still zero (the local path never
+// touches them)
+int Frame::to_global() {
+    local = false;
+    g_fallbacks.fetch_add(1, std::memory_order_relaxed);
+    if (hipMemsetAsync(gs.ctrl, 0, sizeof(uint32_t) * (size_t)dsort_head_words(), s) != hipSuccess)
+        return fail(GSR_ERR_DEVICE, "depth sort control reset failed");
+    {
+        StageTimer st(1, s);
+        launch_depth_sort(in.P, gs, nullptr, nullptr, td->pinned_dev + kHostErr, s, nullptr);
+    }
+    return check("depth sort", debug, s);
+}
+
+// the binning from the superblock scatter on, the tile order and render_fwd, at capacity cap
+int Frame::bin_and_render(int64_t cap, bool counted) {
+    const int P = in.P;
+    uint32_t *const pinned_dev = td->pinned_dev;
+    const uint32_t tbs = !local && P > 0 ? tb_req : 0u;
+    tbsplit_armed = tbs != 0u;
+    // backward / forward items are numbered tile + T * segment (32 bits)
+    seg_used = seg_req && (uint64_t)T * (uint64_t)(cap / seg_req + 1) < (1ull << 32) ? seg_req : 0u;
+    const uint32_t fseg_used =
+        fseg_req && cap > 0 && (uint64_t)T * (uint64_t)(cap / fseg_req + 1) < (1ull << 32) ? fseg_req : 0u;
+    fsplit_armed = fseg_used != 0u;
+    size_t bbytes = 0;
+    carve_binning(nullptr, cap, &bbytes, seg_used, fseg_used);
+    void *bbase = binning_buffer(resize_ctx, bbytes);
+    if (!bbase) return fail(GSR_ERR_ALLOCATION, "binning buffer allocation failed");
+    BinningState bs = carve_binning(bbase, cap, nullptr, seg_used, fseg_used);
+    // P == 0: no depth sort ran, its control words are not initialised (no capacity test)
+    bs.kdev = P > 0 ? dsort_K_word(gs) : nullptr;
+    int r;
+    {
+        StageTimer st(2, s);
+        if (!local && !counted)
+            launch_binning_count(P, cam, gs, false, FrameWords{nullptr, nullptr, nullptr}, s, tbs,
+                                 pinned_dev + kHostSBList);
+        launch_binning_scatter(P, cam, gs, bs, local, s);
+    }
+    if ((r = check("binning (superblocks)", debug, s))) return r;
+    {
+        StageTimer st(3, s);
+        // long superblock lists in slices beside tile_bin (a second side stream: the first may
+        // still carry the colour pass)
+        Side ts;
+        const bool tfork = tbs != 0u && dev->side(1, &ts);
+        if (tfork && !ts.fork_from(s)) return fail(GSR_ERR_DEVICE, "side stream fork failed");
+        launch_binning_tiles(P, cam, gs, bs, is, local, dsort_maxsb_word(gs), s, tbs != 0u, tfork ? ts.st : nullptr);
+        if (tfork && !(ts.record_join() && ts.join_into(s))) return fail(GSR_ERR_DEVICE, "side stream join failed");
+    }
+    if ((r = check("binning (tiles)", debug, s))) return r;
+    // forward segments: the worker pool launched now, on the second side stream once the binning
+    // (and the colour pass) are done, so its workgroups are resident before render_fwd's grid
+    // fills the CUs; they start on the queue when tile_order releases it.  Joined after render_fwd.
+    Side ws;
+    bool early = false;
+    if (fseg_used && g_fwd_early_workers.load(std::memory_order_relaxed) && dev->side(1, &ws)) {
+        if (!ws.fork_from(s) || (join_pending && hipStreamWaitEvent(ws.st, color.join, 0) != hipSuccess))
+            return fail(GSR_ERR_DEVICE, "side stream fork failed");
+        launch_render_fwd_workers(cam, gs, bs, is, background, out_color, out_invdepth, need_bwd, seg_used,
+                                  fseg_used, ws.st, dsort_fwdready_word(gs), spin);
+        if (!ws.record_join()) return fail(GSR_ERR_DEVICE, "side stream join record failed");
+        early = true;
+    }
+    {
+        StageTimer st(4, s);
+        // forward order: by list length (and the backward's class counters zeroed)
+        launch_tile_order(is.ranges, T, 4, is.tile_ids, s, bs.kdev, bs.cap,
+                          need_bwd ? is.bwd_cnt : nullptr, is.bwd_cnt + kFwdItemsWord, bs.point_list, seg_used,
+                          fseg_used, P > 0 ? pinned_dev + kHostTileList : nullptr,
+                          early ? dsort_fwdready_word(gs) : nullptr, fseg_min);
+    }
+    if ((r = check("tile order", debug, s))) return r;
+    if (join_pending) {
+        join_pending = false;
+        if (!color.join_into(s)) return fail(GSR_ERR_DEVICE, "side stream join failed");
+    }
+    {
+        StageTimer st(5, s);
+        // forward segments: the worker pool on the side stream, beside render_fwd (which skips the
+        // split tiles); joined before anything reads the frame
+        Side late;
+        const bool forked = fseg_used && !early && dev->side(0, &late);
+        if (forked && !late.fork_from(s)) return fail(GSR_ERR_DEVICE, "side stream fork failed");
+        launch_render_fwd(cam, gs, bs, is, background, out_color, out_invdepth, s, need_bwd, seg_used, fseg_used,
+                          forked ? late.st : s, early, fseg_min, spin);
+        // the early pool's workers may have given up on the ready word (the two streams did not
+        // run concurrently): a small second launch on this stream, after tile_order, takes any
+        // item still queued -- no frame depends on the streams' concurrency
+        if (early)
+            launch_render_fwd_cleanup(cam, gs, bs, is, background, out_color, out_invdepth, need_bwd, seg_used,
+                                      fseg_used, s, spin);
+        if (forked && !(late.record_join() && late.join_into(s))) return fail(GSR_ERR_DEVICE, "side stream join failed");
+        if (early && !ws.join_into(s)) return fail(GSR_ERR_DEVICE, "side stream join failed");
+    }
+    return check("render", debug, s);
+}
+}  // namespace
+
+int gsr::ForwardCall::run(gsr_resize_fn geom_buffer, gsr_resize_fn binning_buffer, gsr_resize_fn image_buffer,
+                           void *resize_ctx, int P, int D, int M, const float *background, int width, int height,
+                           const float *means3D, const float *shs, const float *colors_precomp,
+                           const float *opacities, const float *scales, float scale_modifier,
+                           const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
+                           const float *projmatrix, const float *cam_pos, float tan_fovx, float tan_fovy,
+                           int prefiltered, float *out_color, float *out_invdepth, int *radii,
+                           const int *render_indices, const int *parent_indices,
+                           const float *interpolation_weights, const int *num_node_kids, int num_render,
+                           int debug, void *stream, int64_t *num_rendered, unsigned flags) {
+    (void)prefiltered;
+    (void)num_node_kids;  // accepted; render_post's blend (which this reproduces) does not read it
+    HostScope host_scope(10);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (flags & ~(unsigned)GSR_FWD_NO_BACKWARD) return fail(GSR_ERR_INVALID_ARGUMENT, "unknown forward flags");
+    // the backward's launch order (render_fwd's work classes) is built only for a frame a backward
+    // may follow (GSR_FWD_NO_BACKWARD not set); clear_acc: such a frame in atomic mode, whose backward
+    // adds into the device's accumulator rows (they are all zero between backwards, AccRows)
+    const bool need_bwd = !(flags & GSR_FWD_NO_BACKWARD);
+    const bool det_fwd = g_deterministic.load(std::memory_order_relaxed) != 0;
+    const bool clear_acc = need_bwd && !det_fwd;
+    if (num_rendered) *num_rendered = 0;
+    int rc = validate_common(P, D, M, shs, colors_precomp, scales, rotations, cov3D_precomp, width, height);
+    if (rc) return rc;
+    if ((rc = validate_cut(num_render, P, shs, scales, rotations, render_indices, parent_indices,
+                           interpolation_weights)))
+        return rc;
+    if (!geom_buffer || !binning_buffer || !image_buffer)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "resize callbacks must be non-NULL");
+    if (!background || !out_color || !viewmatrix || !projmatrix || !cam_pos || (P > 0 && !radii))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (P > 0 && (!means3D || !opacities))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "NULL means3D / opacities");
+
+    // Hierarchy cut: the rasterizer renders the num_render rows blended from (render_indices,
+    // parent_indices, interpolation_weights) over the P input rows -- render_post's LOD blend
+    // (gaussian_renderer/__init__.py:200-243) done here, into the geometry buffer.
+    const int64_t Nin = P;
+    const int R = num_render;
+    if (R > 0) P = R;
+    Frame f{s, debug, need_bwd, background, out_color, out_invdepth, binning_buffer, resize_ctx};  // the rest zero
+    GaussianInputs &in = f.in;
+    in = GaussianInputs{P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                        scale_modifier, raw_params ? 1 : 0};
+    // render_post's blend fused into the preprocess and the SH colour pass (the cut's rows read in
+    // place, no R-row copy written and re-read) for frames no backward follows (render_hierarchy.py's
+    // no_grad frames); a frame a backward may follow keeps the blended rows in its geometry buffer,
+    // where the backward reads them
+    const bool fuse_cut = R > 0 && !need_bwd && cut_fusable(in);
+
+    const Camera &cam = f.cam = make_camera(viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, width, height);
+    const int T = f.T = cam.gx * cam.gy;
+    const int npix = width * height;
+
+    size_t ibytes = 0;
+    const size_t gbytes = geom_bytes(P, cam.gx, cam.gy, fuse_cut ? 0 : R, M);
+    if (!sb_grid_supported(sb_grid(cam.gx, cam.gy, P)))
+        return fail(GSR_ERR_UNSUPPORTED, "image too large for the superblock grid");
+    carve_image(nullptr, T, npix, &ibytes);
+    void *gbase = geom_buffer(resize_ctx, gbytes);
+    void *ibase = image_buffer(resize_ctx, ibytes);
+    if (!gbase || !ibase) return fail(GSR_ERR_ALLOCATION, "geometry/image buffer allocation failed");
+    const GeomState &gs = f.gs = carve_geom(gbase, P, cam.gx, cam.gy, nullptr);
+    note_forward_geom(gbase, need_bwd, clear_acc);
+    f.is = carve_image(ibase, T, npix, nullptr);
+    if (in.raw && (R > 0 || cov3D_precomp))
+        return fail(GSR_ERR_UNSUPPORTED, "raw parameters with a hierarchy cut or precomputed covariances");
+    if (R > 0 && !fuse_cut) {
+        const CutRows cr = cut_rows_of(gbase, P, cam.gx, cam.gy, M);
+        if ((rc = gsr_interpolate_cut_forward(Nin, M, R, 0, render_indices, parent_indices, interpolation_weights,
+                                              means3D, scales, rotations, opacities, shs, cr.means, cr.scales,
+                                              cr.rots, cr.opac, cr.shs, stream)))
+            return rc;
+        in.means3D = cr.means;
+        in.scales = cr.scales;
+        in.rotations = cr.rots;
+        in.opacities = cr.opac;
+        in.shs = cr.shs;
+        if ((rc = check("hierarchy cut blend", debug, s))) return rc;
+    }
+    if (fuse_cut) in.cut = CutRef{render_indices, parent_indices, interpolation_weights, Nin};
+
+    // the calling thread's device: its side streams, and this thread's pinned words and capacity hint
+    Device *const dev = f.dev = current_device();
+    const bool split = P > 0 && color_split_supported(in) && dev && dev->side(0, &f.color);
+    if (fuse_cut && !split) return fail(GSR_ERR_DEVICE, "hierarchy cut: the fused blend needs the SH colour pass");
+    // Depth order (binning.hip): the local sort (level 1 in index order, each superblock list sorted
+    // in LDS) unless the frame is in deterministic mode (its backward needs the global sort's
+    // record offsets) or the global sort is forced; a local frame whose longest SB list exceeds
+    // what the LDS sort holds is re-run through the global sort.
+    bool &local = f.local = P > 0 && g_binning_mode.load(std::memory_order_relaxed) == 0 && !det_fwd;
+    const ColorPlan color = color_plan(P, local, split, dev);
+    f.color_blocks = color.blocks;
+    // A fused hierarchy cut whose colour pass forks early (config 5): forked before the preprocess,
+    // so it overlaps the preprocess as well; it then colours every row (no radii yet: a cut frame's
+    // rows are all in view) and writes only the colour quarter of each render record and the clamp
+    // bits, which the preprocess leaves to it.  Config 5's raster part 2.30 -> 2.28 ms (r06zt,
+    // interleaved; the pass itself 1.44 -> 1.85 ms, longer but off the critical path).
+    const bool pre_fork = fuse_cut && split && color.early;
+    if (pre_fork && (rc = f.fork_color(nullptr))) return rc;
+    {
+        StageTimer st(0, s);
+        launch_preprocess(in, cam, gs, radii, s, split);
+    }
+    if ((rc = check("preprocess", debug, s))) return rc;
+    if (split && color.early && !pre_fork && (rc = f.fork_color(radii))) return rc;
+    // K sizes the point list.  With a capacity hint from this device's previous frame the binning
+    // and the forward render are queued first and K is read afterwards (the GPU never waits on
+    // the host's hand-off); kernels that would overrun the capacity exit at once (they compare the
+    // device's K / instance totals with bs.cap) and the frame's binning and render are queued
+    // again at the real K.  Without a hint (first frame, debug) K is read before the binning.
+    if (!dev) return fail(GSR_ERR_DEVICE, "no current device");
+    ThreadDevice &td = *(f.td = &thread_device(dev));
+    const bool defer = P > 0 && !debug && td.khint > 0;
+    if (P > 0) {
+        if ((rc = td.ensure())) return rc;
+        // deferred K: no event -- its marker packet cost a ~7 us gap before the first sort pass;
+        // the host polls the pinned word the upsweep / column scan stores instead (read_K)
+        f.k_ready = defer ? nullptr : td.k_ready;
+        __atomic_store_n(&td.pinned[kHostWide], 0u, __ATOMIC_RELAXED);
+        __atomic_store_n(&td.pinned[kHostK], kKPending, __ATOMIC_SEQ_CST);
+    }
+    if (local) {
+        {
+            StageTimer st(1, s);  // level-1 counts, SB bases, K
+            launch_binning_count(P, cam, gs, true, FrameWords{dsort_K_word(gs), dsort_maxsb_word(gs), td.pinned_dev}, s);
+            if (f.k_ready) (void)hipEventRecord(f.k_ready, s);
+        }
+        if ((rc = check("binning (counts)", debug, s))) return rc;
+    } else if (P > 0) {
+        {
+            StageTimer st(1, s);
+            launch_depth_sort(P, gs, td.pinned_dev + kHostK, td.pinned_dev + kHostWide, td.pinned_dev + kHostErr, s,
+                              f.k_ready);
+        }
+        if ((rc = check("depth sort", debug, s))) return rc;
+    }
+    f.have_K = P == 0;
+    if (P > 0 && !defer) {
+        if ((rc = f.read_K())) return rc;
+        if (local && f.maxsb > (uint32_t)sort_cap() && (rc = f.to_global())) return rc;
+    }
+    if (split && !color.early && (rc = f.fork_color(radii))) return rc;
+    f.seg_req = need_bwd && bwd_segments_supported() ? g_bwd_seg.load(std::memory_order_relaxed) : 0u;
+    f.fseg_req = fwd_segments_supported() ? g_fwd_seg.load(std::memory_order_relaxed) : 0u;
+    f.tb_req = GSR_TB_SPLIT;  // the list length past which tile_bin slices a superblock (0: off)
+    // the split's minimum list length, read once per frame: tile_order's queue, render_fwd's skip test
+    // and the gate must agree even if gsr_set_fwd_split_min runs meanwhile
+    f.fseg_min = f.fseg_req ? fseg_min_len(f.fseg_req) : 0u;
+    f.spin = fwd_spin(td.pinned_dev);
+    if (P > 0) td.split_gate(f.fseg_min, &f.fseg_req, &f.tb_req);
+    const int64_t cap0 = defer ? td.khint : f.K;
+    if ((rc = f.bin_and_render(cap0, false))) return rc;
+    if (!f.have_K && (rc = f.read_K())) return rc;
+    const int64_t K = f.K;
+    if (debug && P > 0) {  // the binning's instance total must be K (the kernels' capacity test is on K)
+        uint32_t bi = 0;
+        if (hipMemcpy(&bi, gs.sb_base_i + gs.sb.nsb, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(GSR_ERR_DEVICE, "binning total copy failed");
+        if ((int64_t)bi != K) return fail(GSR_ERR_DEVICE, "binning: superblock instance total differs from K");
+    }
+    if (P > 0) g_frames.fetch_add(1, std::memory_order_relaxed);
+    if (f.fsplit_armed) g_fsplit_frames.fetch_add(1, std::memory_order_relaxed);
+    if (f.tbsplit_armed) g_tbsplit_frames.fetch_add(1, std::memory_order_relaxed);
+    if (local && f.maxsb > (uint32_t)sort_cap()) {
+        // an SB list too long for the LDS sort (the sort kernel wrote nothing): the frame again
+        // through the global depth sort, at the capacity it needs
+        if ((rc = f.to_global())) return rc;
+        if ((rc = f.bin_and_render(std::max(K, cap0), false))) return rc;
+    } else if (K > cap0) {  // the capacity was short: again at K
+        g_reruns.fetch_add(1, std::memory_order_relaxed);
+        // global sort: sb_colscan's last-workgroup counter (a depth-sort control word the
+        // preprocess zeroes once per frame) must start from zero again; local sort: the counts and
+        // SB bases stand, only the scatter and the LDS sort re-run
+        if (!local && hipMemsetAsync(dsort_aux_word(gs), 0, sizeof(uint32_t), s) != hipSuccess)
+            return fail(GSR_ERR_DEVICE, "binning counter reset failed");
+        if ((rc = f.bin_and_render(K, local))) return rc;
+    }
+    note_forward_seg(ibase, f.seg_used);  // the re-run's segment length (its capacity may differ)
+    if (P > 0 && local) g_local_frames.fetch_add(1, std::memory_order_relaxed);
+    if (P > 0) td.note_K(K);
+    if (num_rendered) *num_rendered = K;
+    return GSR_OK;
+}
+
+int gsr::BackwardCall::run(gsr_resize_fn scratch, void *resize_ctx, int P, int D, int M, int64_t R_inst,
+                            const float *background, int width, int height, const float *means3D,
+                            const float *shs, const float *colors_precomp, const float *scales,
+                            float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                            const float *viewmatrix, const float *projmatrix, const float *cam_pos,
+                            float tan_fovx, float tan_fovy, const int *radii, void *geom_buffer,
+                            void *binning_buffer, void *image_buffer, const float *dL_dpix,
+                            const float *dL_dinvdepth, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
+                            float *dL_dmeans3D, float *dL_dcov3D, float *dL_dsh, float *dL_dscales,
+                            float *dL_drotations, const int *render_indices, const int *parent_indices,
+                            const float *interpolation_weights, const int *num_node_kids, int num_render,
+                            int debug, void *stream) {
+    (void)num_node_kids;
+    HostScope host_scope(11);
+    act_done = false;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int rc = validate_common(P, D, M, shs, colors_precomp, scales, rotations, cov3D_precomp, width, height);
+    if (rc) return rc;
+    if ((rc = validate_cut(num_render, P, shs, scales, rotations, render_indices, parent_indices,
+                           interpolation_weights)))
+        return rc;
+    if (R_inst < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "num_rendered must be >= 0");
+    if (!scratch) return fail(GSR_ERR_INVALID_ARGUMENT, "scratch callback must be non-NULL");
+    if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dpix)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "NULL state buffer / dL_dpix");
+    if (P > 0 && !radii) return fail(GSR_ERR_INVALID_ARGUMENT, "NULL radii");
+    if (P > 0 && (!dL_dmeans2D || !dL_dopacity || !dL_dmeans3D || (!shs && !dL_dcolors) ||
+                  (cov3D_precomp && !dL_dcov3D)))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "NULL gradient output");
+    if (P > 0 && shs && !dL_dsh) return fail(GSR_ERR_INVALID_ARGUMENT, "NULL dL_dsh");
+    if (P > 0 && !cov3D_precomp && (!dL_dscales || !dL_drotations))
+        return fail(GSR_ERR_INVALID_ARGUMENT, "NULL dL_dscales / dL_drotations");
+    Device *const dev = current_device();
+    if ((rc = sticky_sort_error(dev))) return rc;
+    const uint8_t uncleared = forward_uncleared(geom_buffer);
+    if (uncleared == kNoBackward)
+        return fail(GSR_ERR_INVALID_ARGUMENT, "backward of a forward made with GSR_FWD_NO_BACKWARD (its accumulator "
+                                              "rows were not cleared); run the forward without the flag");
+
+    const int64_t Nin = P;
+    const int R = num_render;
+    const float *rotations_in = rotations;
+    if (R > 0) P = R;
+    const Camera cam = make_camera(viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, width, height);
+    const int T = cam.gx * cam.gy;
+    const GeomState gs = carve_geom(geom_buffer, P, cam.gx, cam.gy, nullptr);
+    const BinningState bs = carve_binning(binning_buffer, R_inst, nullptr);
+    const ImageState is = carve_image(image_buffer, T, width * height, nullptr);
+    // a frame's accumulation mode is the one in force at its forward: one forwarded in
+    // deterministic mode has no cleared accumulators (record path), one forwarded in atomic mode
+    // may have no record offsets (the local sort computes none)
+    const bool atomic = uncleared != kDeterministicFwd;
+    size_t sbytes = 0;
+    const bool list = live_list();  // read once: the carve must match the size
+    carve_bwd(nullptr, R_inst, P, atomic, &sbytes, list);
+    // hierarchy cut: gradients of the R blended rows first, then scattered to the input rows
+    size_t cut_off = 0;
+    if (R > 0) {
+        Carver c(nullptr);
+        c.off = sbytes;
+        carve_cut(c, R, M);
+        cut_off = sbytes;
+        sbytes = align_up(c.off, 256);
+    }
+    void *sbase = scratch(resize_ctx, std::max<size_t>(sbytes, 256));  // atomic mode: the live masks only
+    if (!sbase) return fail(GSR_ERR_ALLOCATION, "backward scratch allocation failed");
+    BwdScratch sc = carve_bwd(sbase, R_inst, P, atomic, nullptr, list);
+    // atomic mode: the device's rows are this backward's until it has queued their consumer
+    AccLease lease(atomic && P > 0 ? dev : nullptr);
+    if (atomic && P > 0 && !(sc.acc = lease.rows(s, (size_t)P)))
+        return fail(GSR_ERR_ALLOCATION, "backward accumulator rows allocation failed");
+
+    // sparse rows only for plain frames (the cut's rows are scattered to the input rows below)
+    GaussianGrads out{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
+                      dL_drotations, sparse_rows && R == 0 ? 1 : 0};
+    CutRows rows{}, grows{};
+    if (R > 0) {
+        rows = cut_rows_of(geom_buffer, P, cam.gx, cam.gy, M);
+        Carver c(sbase);
+        c.off = cut_off;
+        grows = carve_cut(c, R, M);
+        means3D = rows.means;
+        scales = rows.scales;
+        rotations = rows.rots;
+        shs = rows.shs;
+        out.dmeans3D = grows.means;
+        out.dscales = grows.scales;
+        out.drots = grows.rots;
+        out.dopacity = grows.opac;
+        out.dsh = grows.shs;
+        // means2D: the rendered rows' screen-space gradient lands in rows [0, R) of the input's
+        // gradient (render_post slices means2D[:R + skybox] the same way); the rest is zero
+        if (Nin > R && hipMemsetAsync(dL_dmeans2D + 3 * (size_t)R, 0, sizeof(float) * 3 * (size_t)(Nin - R), s) !=
+                           hipSuccess)
+            return fail(GSR_ERR_DEVICE, "means2D gradient clear failed");
+    }
+    if (raw_params && (R > 0 || cov3D_precomp))
+        return fail(GSR_ERR_UNSUPPORTED, "raw parameters with a hierarchy cut or precomputed covariances");
+    GaussianInputs in{P, D, M, means3D, shs, colors_precomp, nullptr, scales, rotations, cov3D_precomp,
+                      scale_modifier, raw_params ? 1 : 0};
+    bool zeroed = false;
+    ZeroRows zr{};
+    {
+        StageTimer st(6, s);
+        // the dense zero gradient rows go out beside render_bwd's replay (bwd_zero_rows)
+        const uint32_t seg = forward_seg(image_buffer);
+        zeroed = R_inst > 0 && bwd_zero_rows(in, out, sc, gs.live_stamp, (int)bwd_grid(T, R_inst, seg), &zr);
+        if (R_inst > 0)
+            launch_render_bwd(cam, gs, bs, is, radii, background, dL_dpix, dL_dinvdepth, sc, s, zeroed ? &zr : nullptr,
+                              seg);
+    }
+    if ((rc = check("render backward", debug, s))) return rc;
+    {
+        StageTimer st(7, s);
+        act_done = launch_preprocess_bwd(in, cam, gs, is, radii, sc, out, s, zeroed ? &zr : nullptr, act);
+    }
+    if (atomic && P > 0) lease.consumed();  // the consumer zeroes what it reads
+    if ((rc = check("preprocess backward", debug, s))) return rc;
+    if (R > 0) {
+        const size_t n3 = sizeof(float) * 3 * (size_t)Nin;
+        if (hipMemsetAsync(dL_dmeans3D, 0, n3, s) != hipSuccess || hipMemsetAsync(dL_dscales, 0, n3, s) != hipSuccess ||
+            hipMemsetAsync(dL_drotations, 0, sizeof(float) * 4 * (size_t)Nin, s) != hipSuccess ||
+            hipMemsetAsync(dL_dopacity, 0, sizeof(float) * (size_t)Nin, s) != hipSuccess ||
+            hipMemsetAsync(dL_dsh, 0, sizeof(float) * 3 * (size_t)M * Nin, s) != hipSuccess)
+            return fail(GSR_ERR_DEVICE, "gradient clear failed");
+        if ((rc = gsr_interpolate_cut_backward(Nin, M, R, 0, render_indices, parent_indices, interpolation_weights,
+                                               rotations_in, grows.means,
+                                               grows.scales, grows.rots, grows.opac, grows.shs, dL_dmeans3D,
+                                               dL_dscales, dL_drotations, dL_dopacity, dL_dsh, stream)))
+            return rc;
+        if ((rc = check("hierarchy cut blend backward", debug, s))) return rc;
+    }
+    return GSR_OK;
+}
 
 extern "C" {
 
@@ -614,406 +1202,11 @@ int gsr_rasterize_forward_ex(gsr_resize_fn geom_buffer, gsr_resize_fn binning_bu
                              const int *render_indices, const int *parent_indices,
                              const float *interpolation_weights, const int *num_node_kids, int num_render,
                              int debug, void *stream, int64_t *num_rendered, unsigned flags) {
-    (void)prefiltered;
-    (void)num_node_kids;  // accepted; render_post's blend (which this reproduces) does not read it
-    HostScope host_scope(10);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (flags & ~(unsigned)GSR_FWD_NO_BACKWARD) return fail(GSR_ERR_INVALID_ARGUMENT, "unknown forward flags");
-    // the backward's launch order (render_fwd's work classes) is built only for a frame a backward
-    // may follow (GSR_FWD_NO_BACKWARD not set); clear_acc: such a frame in atomic mode, whose backward
-    // adds into the device's accumulator rows (they are all zero between backwards, acc_rows)
-    const bool need_bwd = !(flags & GSR_FWD_NO_BACKWARD);
-    const bool det_fwd = g_deterministic.load(std::memory_order_relaxed) != 0;
-    const bool clear_acc = need_bwd && !det_fwd;
-    if (num_rendered) *num_rendered = 0;
-    int rc = validate_common(P, D, M, shs, colors_precomp, scales, rotations, cov3D_precomp, width, height);
-    if (rc) return rc;
-    if ((rc = validate_cut(num_render, P, shs, scales, rotations, render_indices, parent_indices,
-                           interpolation_weights)))
-        return rc;
-    if (!geom_buffer || !binning_buffer || !image_buffer)
-        return fail(GSR_ERR_INVALID_ARGUMENT, "resize callbacks must be non-NULL");
-    if (!background || !out_color || !viewmatrix || !projmatrix || !cam_pos || (P > 0 && !radii))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (P > 0 && (!means3D || !opacities))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "NULL means3D / opacities");
-
-    // Hierarchy cut: the rasterizer renders the num_render rows blended from (render_indices,
-    // parent_indices, interpolation_weights) over the P input rows -- render_post's LOD blend
-    // (gaussian_renderer/__init__.py:200-243) done here, into the geometry buffer.
-    const int64_t Nin = P;
-    const int R = num_render;
-    if (R > 0) P = R;
-    // render_post's blend fused into the preprocess and the SH colour pass (the cut's rows read in
-    // place, no R-row copy written and re-read) for frames no backward follows (render_hierarchy.py's
-    // no_grad frames); a frame a backward may follow keeps the blended rows in its geometry buffer,
-    // where the backward reads them
-    GaussianInputs probe{P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                         scale_modifier, g_raw_params ? 1 : 0};
-    const bool fuse_cut = R > 0 && !need_bwd && cut_fusable(probe);
-
-    const Camera cam = make_camera(viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, width, height);
-    const int T = cam.gx * cam.gy;
-    const int npix = width * height;
-
-    size_t ibytes = 0;
-    const size_t gbytes = geom_bytes(P, cam.gx, cam.gy, fuse_cut ? 0 : R, M);
-    if (!sb_grid_supported(sb_grid(cam.gx, cam.gy, P)))
-        return fail(GSR_ERR_UNSUPPORTED, "image too large for the superblock grid");
-    carve_image(nullptr, T, npix, &ibytes);
-    void *gbase = geom_buffer(resize_ctx, gbytes);
-    void *ibase = image_buffer(resize_ctx, ibytes);
-    if (!gbase || !ibase) return fail(GSR_ERR_ALLOCATION, "geometry/image buffer allocation failed");
-    const GeomState gs = carve_geom(gbase, P, cam.gx, cam.gy, nullptr);
-    note_forward_geom(gbase, need_bwd, clear_acc);
-    const ImageState is = carve_image(ibase, T, npix, nullptr);
-    if (R > 0 && !fuse_cut) {
-        const CutRows cr = cut_rows_of(gbase, P, cam.gx, cam.gy, M);
-        if ((rc = gsr_interpolate_cut_forward(Nin, M, R, 0, render_indices, parent_indices, interpolation_weights,
-                                              means3D, scales, rotations, opacities, shs, cr.means, cr.scales,
-                                              cr.rots, cr.opac, cr.shs, stream)))
-            return rc;
-        means3D = cr.means;
-        scales = cr.scales;
-        rotations = cr.rots;
-        opacities = cr.opac;
-        shs = cr.shs;
-        if ((rc = check("hierarchy cut blend", debug, s))) return rc;
-    }
-
-    if (g_raw_params && (R > 0 || cov3D_precomp))
-        return fail(GSR_ERR_UNSUPPORTED, "raw parameters with a hierarchy cut or precomputed covariances");
-    GaussianInputs in{P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                      scale_modifier, g_raw_params ? 1 : 0};
-    if (fuse_cut) in.cut = CutRef{render_indices, parent_indices, interpolation_weights, Nin};
-    hipStream_t side = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    // the SH colour pass runs on the side stream, beside the sort and / or the binning
-    const bool split = P > 0 && color_split_supported(in) && side_stream(&side, &fork, &join);
-    if (fuse_cut && !split) return fail(GSR_ERR_DEVICE, "hierarchy cut: the fused blend needs the SH colour pass");
-    SideJoin sj;
-#ifndef GSR_COLOR_LOCAL_BLOCKS
-#define GSR_COLOR_LOCAL_BLOCKS 128  // local-sort frames: the colour pass's persistent grid beside the binning
-#endif
-    // Depth order (binning.hip): the local sort (level 1 in index order, each superblock list sorted
-    // in LDS) unless the frame is in deterministic mode (its backward needs the global sort's
-    // record offsets) or the global sort is forced; a local frame whose longest SB list exceeds
-    // what the LDS sort holds is re-run through the global sort.
-    bool local = P > 0 && g_binning_mode.load(std::memory_order_relaxed) == 0 && !det_fwd;
-    // The depth sort runs one 1024-thread workgroup per 8192 keys (dsort_blocks) and leaves the
-    // other CUs idle: when it leaves a good share of them, the SH colour pass forks right after the
-    // preprocess as a persistent grid on those CUs (1M Gaussians: 123 sort workgroups, 128 colour
-    // blocks; 2640 -> 2696 Mpix/s, 133 blocks already slowed the sort); otherwise it forks after the sort, beside the
-    // binning, at full width.  Local-sort frames fork it right after the preprocess too, as a
-    // persistent grid of GSR_COLOR_LOCAL_BLOCKS blocks beside the binning.
-    int color_blocks = 0;
-    bool color_early = false;
-    if (local && split) {
-        color_early = true;
-        color_blocks = GSR_COLOR_LOCAL_BLOCKS;
-    } else if (split) {
-        // workgroups are dealt round-robin over the 8 XCDs: leave every XCD room for its share
-        // of the sort's workgroups (123 of them -> 16 per XCD -> 8 x (32 - 16) = 128 colour blocks)
-        const int per_xcd = device_cus() / 8;
-        const int free_cus = 8 * (per_xcd - (dsort_blocks(P) + 7) / 8);
-        if (free_cus >= 2 * per_xcd) {
-            color_early = true;
-            color_blocks = free_cus;
-        } else {
-            // the sort fills the chip (large P).  Two rounds of it or more (config 5's 7.46M rows):
-            // the colour pass forks right after the preprocess, so it overlaps the sort as well
-            // as the binning (config 5 3.62 -> 3.51 ms, r05f); config 3's 3M-row frames measured
-            // no gain (55.0 vs 55.3 s), so they keep the fork after the sort.  Either way a full
-            // grid of 8-wave blocks.
-            color_early = dsort_blocks(P) >= 2 * device_cus();
-            color_blocks = 0;
-        }
-    }
-    auto fork_color = [&](const int *vis_radii) -> int {
-        // fork: the SH colours stream in beside latency-bound main-stream stages; joined before render_fwd
-        if (hipEventRecord(fork, s) != hipSuccess || hipStreamWaitEvent(side, fork, 0) != hipSuccess)
-            return fail(GSR_ERR_DEVICE, "side stream fork failed");
-        {
-            StageTimer st(8, side);
-            launch_preprocess_color(in, cam, gs, vis_radii, side, color_blocks);
-        }
-        if (hipEventRecord(join, side) != hipSuccess) return fail(GSR_ERR_DEVICE, "side stream join record failed");
-        sj.s = s;
-        sj.join = join;
-        sj.pending = true;
-        return check("preprocess colour", debug, side);
-    };
-    // A fused hierarchy cut whose colour pass forks early (config 5): forked before the preprocess,
-    // so it overlaps the preprocess as well; it then colours every row (no radii yet: a cut frame's
-    // rows are all in view) and writes only the colour quarter of each render record and the clamp
-    // bits, which the preprocess leaves to it.  Config 5's raster part 2.30 -> 2.28 ms (r06zt,
-    // interleaved; the pass itself 1.44 -> 1.85 ms, longer but off the critical path).
-    const bool pre_fork = fuse_cut && split && color_early;
-    if (pre_fork && (rc = fork_color(nullptr))) return rc;
-    {
-        StageTimer st(0, s);
-        launch_preprocess(in, cam, gs, radii, s, split);
-    }
-    if ((rc = check("preprocess", debug, s))) return rc;
-    if (split && color_early && !pre_fork && (rc = fork_color(radii))) return rc;
-    // K sizes the point list.  With a capacity hint from this device's previous frame the binning
-    // and the forward render are queued first and K is read afterwards (the GPU never waits on
-    // the host's hand-off); kernels that would overrun the capacity exit at once (they compare the
-    // device's K / instance totals with bs.cap) and the frame's binning and render are queued
-    // again at the real K.  Without a hint (first frame, debug) K is read before the binning.
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesK)
-        return fail(GSR_ERR_DEVICE, "no current device");
-    const bool defer = P > 0 && !debug && g_khint[dev] > 0;
-    hipEvent_t k_ready = nullptr;
-    if (P > 0) {
-        if (!g_pinned) {
-            if (hipHostMalloc(reinterpret_cast<void **>(&g_pinned), kHostWords * sizeof(uint32_t),
-                              hipHostMallocCoherent) != hipSuccess ||
-                hipHostGetDevicePointer(reinterpret_cast<void **>(&g_pinned_dev), g_pinned, 0) != hipSuccess)
-                return fail(GSR_ERR_ALLOCATION, "pinned host allocation failed");
-            for (int k = 0; k < kHostWords; k++) g_pinned[k] = 0u;
-            for (int d = 0; d < kMaxDevicesK; d++) g_long_tile_at[d] = g_long_sb_at[d] = -2 * kSplitMemory;
-        }
-        if (!g_k_ready[dev] && hipEventCreateWithFlags(&g_k_ready[dev], hipEventDisableTiming) != hipSuccess)
-            return fail(GSR_ERR_DEVICE, "event creation failed");
-        // deferred K: no event -- its marker packet cost a ~7 us gap before the first sort pass;
-        // the host polls the pinned word the upsweep / column scan stores instead (read_K)
-        k_ready = defer ? nullptr : g_k_ready[dev];
-        __atomic_store_n(&g_pinned[kHostWide], 0u, __ATOMIC_RELAXED);
-        __atomic_store_n(&g_pinned[kHostK], kKPending, __ATOMIC_SEQ_CST);
-    }
-    const FrameWords fw_local{dsort_K_word(gs), dsort_maxsb_word(gs), g_pinned_dev};
-    const FrameWords fw_none{nullptr, nullptr, nullptr};
-    if (local) {
-        {
-            StageTimer st(1, s);  // level-1 counts, SB bases, K
-            launch_binning_count(P, cam, gs, true, fw_local, s);
-            if (k_ready) (void)hipEventRecord(k_ready, s);
-        }
-        if ((rc = check("binning (counts)", debug, s))) return rc;
-    } else if (P > 0) {
-        {
-            StageTimer st(1, s);
-            launch_depth_sort(P, gs, g_pinned_dev + kHostK, g_pinned_dev + kHostWide, g_pinned_dev + kHostErr, s,
-                              k_ready);
-        }
-        if ((rc = check("depth sort", debug, s))) return rc;
-    }
-    int64_t K = 0;
-    uint32_t maxsb = 0;
-    bool have_K = P == 0;
-    auto read_K = [&]() -> int {
-        const auto t_wait = std::chrono::steady_clock::now();
-        if (k_ready) {
-            if (hipEventSynchronize(k_ready) != hipSuccess) return fail(GSR_ERR_DEVICE, "num_rendered wait failed");
-        } else {
-            // the frame is queued; the upsweep's (column scan's) last workgroup stores K into the
-            // pinned word (it is normally there already: the host runs ahead of the GPU).  A drained
-            // stream with the word still pending falls through to the device copy below.
-            while (__atomic_load_n(&g_pinned[kHostK], __ATOMIC_SEQ_CST) == kKPending) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) return fail(GSR_ERR_DEVICE, "num_rendered wait failed");
-                std::this_thread::yield();
-            }
-        }
-        g_kwait_ns.fetch_add(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() -
-                                                                                   t_wait).count(),
-                             std::memory_order_relaxed);
-        uint32_t k = __atomic_load_n(&g_pinned[kHostK], __ATOMIC_ACQUIRE);
-        uint32_t m = __atomic_load_n(&g_pinned[kHostMaxSB], __ATOMIC_ACQUIRE);
-        if (k == kKPending) {  // not expected: read the device copies instead (a local frame's K
-                               // word may read "capacity short": its instance total is K)
-            const uint32_t *kw = local ? gs.sb_base_i + gs.sb.nsb : dsort_K_word(gs);
-            if (hipMemcpy(&k, kw, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(&m, dsort_maxsb_word(gs), sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(GSR_ERR_DEVICE, "num_rendered copy failed");
-        }
-        if (debug && !local) {  // the sort passes are complete here (debug syncs after every stage)
-            uint32_t err = 0;
-            if (hipMemcpy(&err, dsort_err_word(gs), sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess || err)
-                return fail(GSR_ERR_DEVICE, "depth sort: a lookback spin timed out");
-        }
-        if ((rc = sticky_sort_error())) return rc;
-        // stored before K by the upsweep (0 on a local-sort frame and when K came from the device copy)
-        if (__atomic_load_n(&g_pinned[kHostWide], __ATOMIC_RELAXED))
-            g_sort_wide_frames.fetch_add(1, std::memory_order_relaxed);
-        K = (int64_t)k;
-        maxsb = local ? m : 0u;
-        have_K = true;
-        return GSR_OK;
-    };
-    // a local frame re-run through the global sort: the head control words (tickets, counters, K)
-    // start from zero again, the lookback status words are still zero (the local path never
-    // touches them)
-    auto to_global = [&]() -> int {
-        local = false;
-        g_fallbacks.fetch_add(1, std::memory_order_relaxed);
-        if (hipMemsetAsync(gs.ctrl, 0, sizeof(uint32_t) * (size_t)dsort_head_words(), s) != hipSuccess)
-            return fail(GSR_ERR_DEVICE, "depth sort control reset failed");
-        {
-            StageTimer st(1, s);
-            launch_depth_sort(P, gs, nullptr, nullptr, g_pinned_dev + kHostErr, s, nullptr);
-        }
-        return check("depth sort", debug, s);
-    };
-    if (P > 0 && !defer) {
-        if ((rc = read_K())) return rc;
-        if (local && maxsb > (uint32_t)sort_cap() && (rc = to_global())) return rc;
-    }
-    if (split && !color_early && (rc = fork_color(radii))) return rc;
-    bool joined = false;
-    const uint32_t seg_req = need_bwd && bwd_segments_supported() ? g_bwd_seg.load(std::memory_order_relaxed) : 0u;
-    uint32_t fseg_req = fwd_segments_supported() ? g_fwd_seg.load(std::memory_order_relaxed) : 0u;
-    uint32_t tb_req = GSR_TB_SPLIT;  // the list length past which tile_bin slices a superblock (0: off)
-    // the split's minimum list length, read once per frame: tile_order's queue, render_fwd's skip test
-    // and the gate must agree even if gsr_set_fwd_split_min runs meanwhile
-    const uint32_t fseg_min = fseg_req ? fseg_min_len(fseg_req) : 0u;
-    const FwdSpin spin = fwd_spin(g_pinned_dev);
-    if (P > 0) {
-        // the split gate: the longest lists of the frames before (whatever the pinned words hold now)
-        const int64_t f = ++g_frame_no[dev];
-        const uint32_t tl = __atomic_load_n(&g_pinned[kHostTileList], __ATOMIC_RELAXED);
-        const uint32_t sl = __atomic_load_n(&g_pinned[kHostSBList], __ATOMIC_RELAXED);
-        if (fseg_req && tl > fseg_min) g_long_tile_at[dev] = f;
-        if (tb_req && sl > tb_req) g_long_sb_at[dev] = f;
-        if (g_split_gate.load(std::memory_order_relaxed)) {
-            if (f - g_long_tile_at[dev] > kSplitMemory) fseg_req = 0;
-            if (f - g_long_sb_at[dev] > kSplitMemory) tb_req = 0;
-        }
-    }
-    uint32_t seg_used = 0;
-    bool fsplit_armed = false, tbsplit_armed = false;
-    auto bin_and_render = [&](int64_t cap, bool counted) -> int {
-        const uint32_t tbs = !local && P > 0 ? tb_req : 0u;
-        tbsplit_armed = tbs != 0u;
-        // backward / forward items are numbered tile + T * segment (32 bits)
-        seg_used = seg_req && (uint64_t)T * (uint64_t)(cap / seg_req + 1) < (1ull << 32) ? seg_req : 0u;
-        const uint32_t fseg_used =
-            fseg_req && cap > 0 && (uint64_t)T * (uint64_t)(cap / fseg_req + 1) < (1ull << 32) ? fseg_req : 0u;
-        fsplit_armed = fseg_used != 0u;
-        size_t bbytes = 0;
-        carve_binning(nullptr, cap, &bbytes, seg_used, fseg_used);
-        void *bbase = binning_buffer(resize_ctx, bbytes);
-        if (!bbase) return fail(GSR_ERR_ALLOCATION, "binning buffer allocation failed");
-        BinningState bs = carve_binning(bbase, cap, nullptr, seg_used, fseg_used);
-        // P == 0: no depth sort ran, its control words are not initialised (no capacity test)
-        bs.kdev = P > 0 ? dsort_K_word(gs) : nullptr;
-        int r;
-        {
-            StageTimer st(2, s);
-            if (!local && !counted)
-                launch_binning_count(P, cam, gs, false, fw_none, s, tbs, g_pinned_dev + kHostSBList);
-            launch_binning_scatter(P, cam, gs, bs, local, s);
-        }
-        if ((r = check("binning (superblocks)", debug, s))) return r;
-        {
-            StageTimer st(3, s);
-            // long superblock lists in slices beside tile_bin (a second side stream: the first may
-            // still carry the colour pass)
-            hipStream_t ts = s;
-            hipEvent_t tf = nullptr, tj = nullptr;
-            const bool tfork = tbs != 0u && side_stream(&ts, &tf, &tj, 1);
-            if (tfork && (hipEventRecord(tf, s) != hipSuccess || hipStreamWaitEvent(ts, tf, 0) != hipSuccess))
-                return fail(GSR_ERR_DEVICE, "side stream fork failed");
-            launch_binning_tiles(P, cam, gs, bs, is, local, dsort_maxsb_word(gs), s, tbs != 0u, tfork ? ts : nullptr);
-            if (tfork && (hipEventRecord(tj, ts) != hipSuccess || hipStreamWaitEvent(s, tj, 0) != hipSuccess))
-                return fail(GSR_ERR_DEVICE, "side stream join failed");
-        }
-        if ((r = check("binning (tiles)", debug, s))) return r;
-        // forward segments: the worker pool launched now, on the second side stream once the binning
-        // (and the colour pass) are done, so its workgroups are resident before render_fwd's grid
-        // fills the CUs; they start on the queue when tile_order releases it.  Joined after render_fwd.
-        hipStream_t ws = s;
-        hipEvent_t wf = nullptr, wj = nullptr;
-        bool early = false;
-        if (fseg_used && g_fwd_early_workers.load(std::memory_order_relaxed) && side_stream(&ws, &wf, &wj, 1)) {
-            if (hipEventRecord(wf, s) != hipSuccess || hipStreamWaitEvent(ws, wf, 0) != hipSuccess ||
-                (split && !joined && hipStreamWaitEvent(ws, join, 0) != hipSuccess))
-                return fail(GSR_ERR_DEVICE, "side stream fork failed");
-            launch_render_fwd_workers(cam, gs, bs, is, background, out_color, out_invdepth, need_bwd, seg_used,
-                                      fseg_used, ws, dsort_fwdready_word(gs), spin);
-            if (hipEventRecord(wj, ws) != hipSuccess) return fail(GSR_ERR_DEVICE, "side stream join record failed");
-            early = true;
-        }
-        {
-            StageTimer st(4, s);
-            // forward order: by list length (and the backward's class counters zeroed)
-            launch_tile_order(is.ranges, T, 4, is.tile_ids, s, bs.kdev, bs.cap,
-                              need_bwd ? is.bwd_cnt : nullptr, is.bwd_cnt + kFwdItemsWord, bs.point_list, seg_used,
-                              fseg_used, P > 0 ? g_pinned_dev + kHostTileList : nullptr,
-                              early ? dsort_fwdready_word(gs) : nullptr, fseg_min);
-        }
-        if ((r = check("tile order", debug, s))) return r;
-        if (split && !joined) {
-            sj.pending = false;
-            joined = true;
-            if (hipStreamWaitEvent(s, join, 0) != hipSuccess) return fail(GSR_ERR_DEVICE, "side stream join failed");
-        }
-        {
-            StageTimer st(5, s);
-            // forward segments: the worker pool on the side stream, beside render_fwd (which skips the
-            // split tiles); joined before anything reads the frame
-            hipStream_t wside = s;
-            hipEvent_t wfork = nullptr, wjoin = nullptr;
-            if (fseg_used && !early && !side_stream(&wside, &wfork, &wjoin)) wside = s;
-            const bool forked = fseg_used && !early && wside != s;
-            if (forked && (hipEventRecord(wfork, s) != hipSuccess || hipStreamWaitEvent(wside, wfork, 0) != hipSuccess))
-                return fail(GSR_ERR_DEVICE, "side stream fork failed");
-            launch_render_fwd(cam, gs, bs, is, background, out_color, out_invdepth, s, need_bwd, seg_used, fseg_used,
-                              wside, early, fseg_min, spin);
-            // the early pool's workers may have given up on the ready word (the two streams did not
-            // run concurrently): a small second launch on this stream, after tile_order, takes any
-            // item still queued -- no frame depends on the streams' concurrency
-            if (early)
-                launch_render_fwd_cleanup(cam, gs, bs, is, background, out_color, out_invdepth, need_bwd, seg_used,
-                                          fseg_used, s, spin);
-            if (forked && (hipEventRecord(wjoin, wside) != hipSuccess || hipStreamWaitEvent(s, wjoin, 0) != hipSuccess))
-                return fail(GSR_ERR_DEVICE, "side stream join failed");
-            if (early && hipStreamWaitEvent(s, wj, 0) != hipSuccess) return fail(GSR_ERR_DEVICE, "side stream join failed");
-        }
-        return check("render", debug, s);
-    };
-    const int64_t cap0 = defer ? g_khint[dev] : K;
-    if ((rc = bin_and_render(cap0, false))) return rc;
-    if (!have_K && (rc = read_K())) return rc;
-    if (debug && P > 0) {  // the binning's instance total must be K (the kernels' capacity test is on K)
-        uint32_t bi = 0;
-        if (hipMemcpy(&bi, gs.sb_base_i + gs.sb.nsb, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(GSR_ERR_DEVICE, "binning total copy failed");
-        if ((int64_t)bi != K) return fail(GSR_ERR_DEVICE, "binning: superblock instance total differs from K");
-    }
-    if (P > 0) g_frames.fetch_add(1, std::memory_order_relaxed);
-    if (fsplit_armed) g_fsplit_frames.fetch_add(1, std::memory_order_relaxed);
-    if (tbsplit_armed) g_tbsplit_frames.fetch_add(1, std::memory_order_relaxed);
-    if (local && maxsb > (uint32_t)sort_cap()) {
-        // an SB list too long for the LDS sort (the sort kernel wrote nothing): the frame again
-        // through the global depth sort, at the capacity it needs
-        if ((rc = to_global())) return rc;
-        if ((rc = bin_and_render(std::max(K, cap0), false))) return rc;
-    } else if (K > cap0) {  // the capacity was short: again at K
-        g_reruns.fetch_add(1, std::memory_order_relaxed);
-        // global sort: sb_colscan's last-workgroup counter (a depth-sort control word the
-        // preprocess zeroes once per frame) must start from zero again; local sort: the counts and
-        // SB bases stand, only the scatter and the LDS sort re-run
-        if (!local && hipMemsetAsync(dsort_aux_word(gs), 0, sizeof(uint32_t), s) != hipSuccess)
-            return fail(GSR_ERR_DEVICE, "binning counter reset failed");
-        if ((rc = bin_and_render(K, local))) return rc;
-    }
-    note_forward_seg(ibase, seg_used);  // the re-run's segment length (its capacity may differ)
-    if (P > 0 && local) g_local_frames.fetch_add(1, std::memory_order_relaxed);
-    // the kernels compare K with a 32-bit capacity: keep the hint representable
-    if (P > 0) {
-        g_khist[dev][g_khead[dev]] = K;
-        g_khead[dev] = (g_khead[dev] + 1) % kKHist;
-        int64_t kmax = 0;
-        for (int i = 0; i < kKHist; i++) kmax = std::max(kmax, g_khist[dev][i]);
-        // the kernels compare K with a 32-bit capacity: keep the hint representable
-        g_khint[dev] = std::min<int64_t>(kmax + kmax / 8 + 4096, (int64_t)UINT32_MAX);
-    }
-    if (num_rendered) *num_rendered = K;
-    return GSR_OK;
+    return ForwardCall{}.run(geom_buffer, binning_buffer, image_buffer, resize_ctx, P, D, M, background, width, height,
+                             means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                             viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_invdepth,
+                             radii, render_indices, parent_indices, interpolation_weights, num_node_kids, num_render,
+                             debug, stream, num_rendered, flags);
 }
 
 int gsr_rasterize_backward(gsr_resize_fn scratch, void *resize_ctx, int P, int D, int M, int64_t R_inst,
@@ -1028,123 +1221,12 @@ int gsr_rasterize_backward(gsr_resize_fn scratch, void *resize_ctx, int P, int D
                            float *dL_drotations, const int *render_indices, const int *parent_indices,
                            const float *interpolation_weights, const int *num_node_kids, int num_render,
                            int debug, void *stream) {
-    (void)num_node_kids;
-    HostScope host_scope(11);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int rc = validate_common(P, D, M, shs, colors_precomp, scales, rotations, cov3D_precomp, width, height);
-    if (rc) return rc;
-    if ((rc = validate_cut(num_render, P, shs, scales, rotations, render_indices, parent_indices,
-                           interpolation_weights)))
-        return rc;
-    if (R_inst < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "num_rendered must be >= 0");
-    if (!scratch) return fail(GSR_ERR_INVALID_ARGUMENT, "scratch callback must be non-NULL");
-    if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dpix)
-        return fail(GSR_ERR_INVALID_ARGUMENT, "NULL state buffer / dL_dpix");
-    if (P > 0 && !radii) return fail(GSR_ERR_INVALID_ARGUMENT, "NULL radii");
-    if (P > 0 && (!dL_dmeans2D || !dL_dopacity || !dL_dmeans3D || (!shs && !dL_dcolors) ||
-                  (cov3D_precomp && !dL_dcov3D)))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "NULL gradient output");
-    if (P > 0 && shs && !dL_dsh) return fail(GSR_ERR_INVALID_ARGUMENT, "NULL dL_dsh");
-    if (P > 0 && !cov3D_precomp && (!dL_dscales || !dL_drotations))
-        return fail(GSR_ERR_INVALID_ARGUMENT, "NULL dL_dscales / dL_drotations");
-    if ((rc = sticky_sort_error())) return rc;
-    const uint8_t uncleared = forward_uncleared(geom_buffer);
-    if (uncleared == kNoBackward)
-        return fail(GSR_ERR_INVALID_ARGUMENT, "backward of a forward made with GSR_FWD_NO_BACKWARD (its accumulator "
-                                              "rows were not cleared); run the forward without the flag");
-
-    const int64_t Nin = P;
-    const int R = num_render;
-    const float *rotations_in = rotations;
-    if (R > 0) P = R;
-    const Camera cam = make_camera(viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, width, height);
-    const int T = cam.gx * cam.gy;
-    const GeomState gs = carve_geom(geom_buffer, P, cam.gx, cam.gy, nullptr);
-    const BinningState bs = carve_binning(binning_buffer, R_inst, nullptr);
-    const ImageState is = carve_image(image_buffer, T, width * height, nullptr);
-    // a frame's accumulation mode is the one in force at its forward: one forwarded in
-    // deterministic mode has no cleared accumulators (record path), one forwarded in atomic mode
-    // may have no record offsets (the local sort computes none)
-    const bool atomic = uncleared != kDeterministicFwd;
-    size_t sbytes = 0;
-    const bool list = live_list();  // read once: the carve must match the size
-    carve_bwd(nullptr, R_inst, P, atomic, &sbytes, list);
-    // hierarchy cut: gradients of the R blended rows first, then scattered to the input rows
-    size_t cut_off = 0;
-    if (R > 0) {
-        Carver c(nullptr);
-        c.off = sbytes;
-        carve_cut(c, R, M);
-        cut_off = sbytes;
-        sbytes = align_up(c.off, 256);
-    }
-    void *sbase = scratch(resize_ctx, std::max<size_t>(sbytes, 256));  // atomic mode: the live masks only
-    if (!sbase) return fail(GSR_ERR_ALLOCATION, "backward scratch allocation failed");
-    BwdScratch sc = carve_bwd(sbase, R_inst, P, atomic, nullptr, list);
-    if (atomic && P > 0 && !(sc.acc = acc_rows(s, (size_t)P)))
-        return fail(GSR_ERR_ALLOCATION, "backward accumulator rows allocation failed");
-
-    // sparse rows only for plain frames (the cut's rows are scattered to the input rows below)
-    GaussianGrads out{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-                      dL_drotations, g_sparse_grad_rows && R == 0 ? 1 : 0};
-    CutRows rows{}, grows{};
-    if (R > 0) {
-        rows = cut_rows_of(geom_buffer, P, cam.gx, cam.gy, M);
-        Carver c(sbase);
-        c.off = cut_off;
-        grows = carve_cut(c, R, M);
-        means3D = rows.means;
-        scales = rows.scales;
-        rotations = rows.rots;
-        shs = rows.shs;
-        out.dmeans3D = grows.means;
-        out.dscales = grows.scales;
-        out.drots = grows.rots;
-        out.dopacity = grows.opac;
-        out.dsh = grows.shs;
-        // means2D: the rendered rows' screen-space gradient lands in rows [0, R) of the input's
-        // gradient (render_post slices means2D[:R + skybox] the same way); the rest is zero
-        if (Nin > R && hipMemsetAsync(dL_dmeans2D + 3 * (size_t)R, 0, sizeof(float) * 3 * (size_t)(Nin - R), s) !=
-                           hipSuccess)
-            return fail(GSR_ERR_DEVICE, "means2D gradient clear failed");
-    }
-    if (g_raw_params && (R > 0 || cov3D_precomp))
-        return fail(GSR_ERR_UNSUPPORTED, "raw parameters with a hierarchy cut or precomputed covariances");
-    GaussianInputs in{P, D, M, means3D, shs, colors_precomp, nullptr, scales, rotations, cov3D_precomp,
-                      scale_modifier, g_raw_params ? 1 : 0};
-    bool zeroed = false;
-    ZeroRows zr{};
-    {
-        StageTimer st(6, s);
-        // the dense zero gradient rows go out beside render_bwd's replay (bwd_zero_rows)
-        const uint32_t seg = forward_seg(image_buffer);
-        zeroed = R_inst > 0 && bwd_zero_rows(in, out, sc, gs.live_stamp, (int)bwd_grid(T, R_inst, seg), &zr);
-        if (R_inst > 0)
-            launch_render_bwd(cam, gs, bs, is, radii, background, dL_dpix, dL_dinvdepth, sc, s, zeroed ? &zr : nullptr,
-                              seg);
-    }
-    if ((rc = check("render backward", debug, s))) return rc;
-    {
-        StageTimer st(7, s);
-        launch_preprocess_bwd(in, cam, gs, is, radii, sc, out, s, zeroed ? &zr : nullptr);
-    }
-    if (atomic && P > 0) acc_rows_consumed();  // the consumer zeroes what it reads
-    if ((rc = check("preprocess backward", debug, s))) return rc;
-    if (R > 0) {
-        const size_t n3 = sizeof(float) * 3 * (size_t)Nin;
-        if (hipMemsetAsync(dL_dmeans3D, 0, n3, s) != hipSuccess || hipMemsetAsync(dL_dscales, 0, n3, s) != hipSuccess ||
-            hipMemsetAsync(dL_drotations, 0, sizeof(float) * 4 * (size_t)Nin, s) != hipSuccess ||
-            hipMemsetAsync(dL_dopacity, 0, sizeof(float) * (size_t)Nin, s) != hipSuccess ||
-            hipMemsetAsync(dL_dsh, 0, sizeof(float) * 3 * (size_t)M * Nin, s) != hipSuccess)
-            return fail(GSR_ERR_DEVICE, "gradient clear failed");
-        if ((rc = gsr_interpolate_cut_backward(Nin, M, R, 0, render_indices, parent_indices, interpolation_weights,
-                                               rotations_in, grows.means,
-                                               grows.scales, grows.rots, grows.opac, grows.shs, dL_dmeans3D,
-                                               dL_dscales, dL_drotations, dL_dopacity, dL_dsh, stream)))
-            return rc;
-        if ((rc = check("hierarchy cut blend backward", debug, s))) return rc;
-    }
-    return GSR_OK;
+    return BackwardCall{}.run(scratch, resize_ctx, P, D, M, R_inst, background, width, height, means3D, shs,
+                              colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                              cam_pos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
+                              dL_dinvdepth, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh,
+                              dL_dscales, dL_drotations, render_indices, parent_indices, interpolation_weights,
+                              num_node_kids, num_render, debug, stream);
 }
 
 int gsr_set_true_scale_gradient(int enable) {
@@ -1198,7 +1280,7 @@ int gsr_set_binning(int mode) {
 
 int gsr_forward_stats(int64_t *out, int n) {
     if (!out || n < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "NULL stats buffer");
-    collect_giveups();
+    collect_giveups(current_device());
     const int64_t v[kFwdStats] = {g_frames.load(), g_reruns.load(), g_local_frames.load(), g_fallbacks.load(),
                                   g_fwd_giveups.load(), g_kwait_ns.load(), g_fsplit_frames.load(),
                                   g_tbsplit_frames.load(), g_sort_wide_frames.load(), g_sort_late_pass.load()};
@@ -1218,13 +1300,7 @@ int gsr_segment_layout_check(int64_t K, int L, int Lf, int64_t *need, int64_t *h
 }
 
 int gsr_reset_capacity_hint(void) {
-    if (g_pinned) g_pinned[kHostTileList] = g_pinned[kHostSBList] = 0u;
-    for (int d = 0; d < kMaxDevicesK; d++) {
-        g_long_tile_at[d] = g_long_sb_at[d] = g_frame_no[d] - 2 * kSplitMemory;
-        g_khint[d] = 0;
-        g_khead[d] = 0;
-        for (int i = 0; i < kKHist; i++) g_khist[d][i] = 0;
-    }
+    for (ThreadDevice &td : t_devices) td.reset();
     return GSR_OK;
 }
 

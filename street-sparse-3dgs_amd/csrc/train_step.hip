@@ -42,7 +42,6 @@ enum Slot {
     kSlots
 };
 
-
 }  // namespace
 }  // namespace gsr
 
@@ -136,9 +135,6 @@ int fail_step(int rc, const char *what) {
     set_last_error(std::string("gsr_train_step: ") + what + ": " + gsr_last_error());
     return rc;
 }
-
-// The rasterizer and the activation backward read the raw parameters and activate them where they
-// are used (GaussianInputs.raw); the Python-driven step writes the activations in a launch of their own.
 
 int invalid(const char *msg) {
     set_last_error(std::string("gsr_train_step: ") + msg);
@@ -236,14 +232,15 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
     int rc;
 
     // render(): activations, rasterizer, exposure of this view (harness.py TrainStep.render).  The
-    // preprocess activates the raw parameters it reads (no activated copy written and re-read)
+    // rasterizer and the activation backward activate the raw parameters where they read them
+    // (GaussianInputs.raw: no activated copy written and re-read, as the Python-driven step does)
     int64_t K = 0;
-    set_raw_params(true);
-    rc = gsr_rasterize_forward_ex(resize_geom, resize_binning, resize_image, ctx, (int)P, a->D, a->M, a->background,
-                                  W, H, a->xyz, a->features, nullptr, a->opacity, a->scaling, 1.0f, a->rotation, nullptr,
-                                  a->viewmatrix, a->projmatrix, a->campos, a->tan_fovx, a->tan_fovy, 0, color, invd,
-                                  radii, nullptr, nullptr, nullptr, nullptr, 0, 0, sv, &K, 0);
-    set_raw_params(false);
+    ForwardCall fwd;
+    fwd.raw_params = true;
+    rc = fwd.run(resize_geom, resize_binning, resize_image, ctx, (int)P, a->D, a->M, a->background, W, H, a->xyz,
+                 a->features, nullptr, a->opacity, a->scaling, 1.0f, a->rotation, nullptr, a->viewmatrix, a->projmatrix,
+                 a->campos, a->tan_fovx, a->tan_fovy, 0, color, invd, radii, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                 sv, &K, 0);
     if (rc) return fail_step(rc, "rasterizer forward");
     const float *E = a->exposure + 12 * (int64_t)a->image_index;
     if (depth_only) {
@@ -292,21 +289,18 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
                           (reinterpret_cast<uintptr_t>(a->features_grad) & 15u) == 0;
     const StepAct act{a->scaling, a->opacity, reinterpret_cast<const float4 *>(a->rotation), a->skybox_rows, radii,
                       a->max_radii2D, a->xyz_gradient_accum, a->denom, flag, 1};
-    set_sparse_grad_rows(sparse_rows);
-    set_raw_params(true);
-    set_step_act(fuse_act ? &act : nullptr);
-    rc = gsr_rasterize_backward(resize_scratch, ctx, (int)P, a->D, a->M, K, a->background, W, H, a->xyz,
-                                a->features, nullptr, a->scaling, 1.0f, a->rotation, nullptr, a->viewmatrix,
-                                a->projmatrix, a->campos, a->tan_fovx, a->tan_fovy, radii, buf_ptr(ctx, kGeom),
-                                buf_ptr(ctx, kBinning), buf_ptr(ctx, kImage), d_color, depth ? d_invd : nullptr,
-                                d_means2D, nullptr, fuse_act ? a->opacity_grad : d_opac, a->xyz_grad, nullptr,
-                                a->features_grad, fuse_act ? a->scaling_grad : d_scales,
-                                fuse_act ? a->rotation_grad : d_rots, nullptr, nullptr, nullptr, nullptr, 0, 0, sv);
-    set_sparse_grad_rows(false);
-    set_raw_params(false);
-    set_step_act(nullptr);
+    BackwardCall bwd;
+    bwd.raw_params = true;
+    bwd.sparse_rows = sparse_rows;
+    bwd.act = fuse_act ? &act : nullptr;
+    rc = bwd.run(resize_scratch, ctx, (int)P, a->D, a->M, K, a->background, W, H, a->xyz, a->features, nullptr,
+                 a->scaling, 1.0f, a->rotation, nullptr, a->viewmatrix, a->projmatrix, a->campos, a->tan_fovx,
+                 a->tan_fovy, radii, buf_ptr(ctx, kGeom), buf_ptr(ctx, kBinning), buf_ptr(ctx, kImage), d_color,
+                 depth ? d_invd : nullptr, d_means2D, nullptr, fuse_act ? a->opacity_grad : d_opac, a->xyz_grad,
+                 nullptr, a->features_grad, fuse_act ? a->scaling_grad : d_scales,
+                 fuse_act ? a->rotation_grad : d_rots, nullptr, nullptr, nullptr, nullptr, 0, 0, sv);
     if (rc) return fail_step(rc, "rasterizer backward");
-    if (fuse_act != step_act_done())
+    if (fuse_act != bwd.act_done)
         return invalid("the rasterizer backward did not take the fused activation backward it was given");
     // otherwise the activation backward on its own; then the sparse Adam and the shrink (:225-241)
     if (!fuse_act &&
