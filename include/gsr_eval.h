@@ -4,8 +4,8 @@
  *
  * Replaces the per-frame metric loop of render_hierarchy_final.py:259-390: compute_metrics (:142-157:
  * psnr / ssim for the whole image, psnr_masked / ssim_masked per depth range and per segmentation
- * category), compute_depth_metrics (:159-173) and the pixel-weighted running sums (:287-385).  LPIPS
- * is not computed.
+ * category), compute_depth_metrics (:159-173) and the pixel-weighted running sums (:287-385).  LPIPS,
+ * the third image metric of compute_metrics, is gsr_lpips.h.
  *
  * A region is one bit of a uint16 plane: bit r of region_bits[p] says pixel p belongs to region r.
  * Regions may overlap.  gsr_eval_depth_range_bits and gsr_eval_color_bits build the reference's two

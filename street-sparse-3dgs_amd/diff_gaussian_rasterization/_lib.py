@@ -177,6 +177,15 @@ HIER_MERGE_SIGNATURES = {
     "gsr_hier_merge_stage_ms": (_i, [ctypes.POINTER(_f), _i]),
 }
 
+# include/gsr_lpips.h (the LPIPS metric around a caller-run trunk); typed by load() like SIGNATURES.  New
+# entry points only: the ABI version stays
+LPIPS_SIGNATURES = {
+    "gsr_lpips_prepare": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "gsr_lpips_tap_scratch_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "gsr_lpips_tap": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gsr_lpips_accumulate": (_i, [_vp, _vp, _i, _vp, _vp]),
+}
+
 ABI_VERSION = 7
 _lib = None
 
@@ -199,7 +208,8 @@ def load(path: str = LIB_PATH):
     except OSError as e:  # pragma: no cover - depends on the host
         raise RasterizerLibraryError(f"failed to load {path}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(GT_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
-                              + list(HIER_BUILD_SIGNATURES.items()) + list(HIER_MERGE_SIGNATURES.items())):
+                              + list(HIER_BUILD_SIGNATURES.items()) + list(HIER_MERGE_SIGNATURES.items())
+                              + list(LPIPS_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

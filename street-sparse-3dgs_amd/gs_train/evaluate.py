@@ -7,8 +7,10 @@ compute_depth_metrics, get_depth_range_mask, the category colour match) and its 
 (:390-438).  A region is one bit of a 16-bit plane; the frame is read once however many regions
 there are, and a whole test set needs one device-to-host read, in Evaluator.result().
 
-LPIPS is out of scope: it needs the VGG weights of lpipsPyTorch, which this package does not carry.
-The report lines are the reference's without the LPIPS field.
+LPIPS is the caller's choice: Evaluator(lpips=LpipsModel...) (gs_train/lpips.py, with the caller's VGG
+and LPIPS weights -- this package carries none) adds the reference's third image metric to every row,
+from one trunk pass per frame, and the report lines are then the reference's field for field.
+Without a model the tables, the result keys and the report lines carry no LPIPS field.
 
 One documented divergence: a region that has pixels in a frame but none where the alpha mask is
 positive has weight 0 and is left out of the sums (the reference would add inf * 0 = NaN).
@@ -148,9 +150,9 @@ class Evaluator:
 
     region_names: one name per region bit, in bit order.  None: the three depth ranges
     (depth_near, depth_medium, depth_far), followed by the six categories when categories=True --
-    the layout add_view builds."""
+    the layout add_view builds.  lpips: a gs_train.lpips.LpipsModel, or None (no LPIPS column)."""
 
-    def __init__(self, region_names=None, categories: bool = False):
+    def __init__(self, region_names=None, categories: bool = False, lpips=None):
         self._standard = region_names is None
         if region_names is None:
             region_names = ["depth_" + n for n in DEPTH_RANGE_NAMES] + (list(CATEGORY_COLORS) if categories else [])
@@ -161,6 +163,8 @@ class Evaluator:
             raise ValueError("region names must be distinct and not 'whole_image'")
         self.categories = bool(categories) and self._standard
         self.totals = None  # (1 + R, 6) float64 on the device of the first frame
+        self.lpips = lpips
+        self.lpips_totals = None  # (1 + R, 2) float64 beside it: sum w lpips, sum w
 
     @property
     def n_regions(self):
@@ -173,6 +177,12 @@ class Evaluator:
             self.totals = torch.zeros((1 + self.n_regions, 6), dtype=torch.float64, device=frame.device)
         check(lib().gsr_eval_accumulate(ptr(frame), 1 + self.n_regions, ptr(self.totals), stream(frame.device)),
               "gsr_eval_accumulate")
+        if self.lpips is not None:
+            from .lpips import accumulate
+            rows = self.lpips.frame(image, gt, alpha_mask, region_bits, self.n_regions)
+            if self.lpips_totals is None:
+                self.lpips_totals = torch.zeros((1 + self.n_regions, 2), dtype=torch.float64, device=frame.device)
+            accumulate(rows, frame, self.lpips_totals)
         return frame
 
     def add_view(self, render_pkg, view, half: bool = False) -> torch.Tensor:
@@ -197,26 +207,35 @@ class Evaluator:
         return self.add(image, gt.to(image.device), None if alpha is None else alpha.to(image.device), depth, gt_depth,
                         bits)
 
-    def result(self, totals=None) -> dict:
+    def result(self, totals=None, lpips_totals=None) -> dict:
         """{name: {psnr, ssim, imae, irmse, pixel_count, image_count}}: each metric's weighted sum
         divided by the summed weight (render_hierarchy_final.py:398-435), None where nothing was
-        evaluated.  The one device-to-host read."""
+        evaluated; with a model also lpips, after ssim.  The one device-to-host read (two with a
+        model)."""
         t = self.totals if totals is None else totals
         rows = [[0.0] * 6] * (1 + self.n_regions) if t is None else torch.as_tensor(t).cpu().tolist()
+        lp = None
+        if self.lpips is not None:
+            lt = self.lpips_totals if lpips_totals is None else lpips_totals
+            lp = [[0.0] * 2] * (1 + self.n_regions) if lt is None else torch.as_tensor(lt).cpu().tolist()
         out = {}
-        for name, r in zip(["whole_image"] + self.region_names, rows):
+        for k, (name, r) in enumerate(zip(["whole_image"] + self.region_names, rows)):
             n = int(r[5])
             m = [v / r[4] if n > 0 else None for v in r[:4]]
-            out[name] = {"psnr": m[0], "ssim": m[1], "imae": m[2], "irmse": m[3], "pixel_count": int(r[4]),
-                         "image_count": n}
+            out[name] = {"psnr": m[0], "ssim": m[1]}
+            if lp is not None:
+                out[name]["lpips"] = lp[k][0] / r[4] if n > 0 else None
+            out[name].update({"imae": m[2], "irmse": m[3], "pixel_count": int(r[4]), "image_count": n})
         return out
 
-    def format(self, totals=None) -> list:
-        """The reference's report lines (render_hierarchy_final.py:403-437) without the LPIPS field."""
-        res = self.result(totals)
+    def format(self, totals=None, lpips_totals=None) -> list:
+        """The reference's report lines (render_hierarchy_final.py:403-437); the LPIPS field is there
+        with a model and absent without."""
+        res = self.result(totals, lpips_totals)
 
         def metrics(r):
-            return (f"PSNR: {r['psnr']:.5f} SSIM: {r['ssim']:.5f} iMAE: {r['imae']:.5f} iRMSE: {r['irmse']:.5f} "
+            lp = f"LPIPS: {r['lpips']:.5f} " if "lpips" in r else ""
+            return (f"PSNR: {r['psnr']:.5f} SSIM: {r['ssim']:.5f} {lp}iMAE: {r['imae']:.5f} iRMSE: {r['irmse']:.5f} "
                     f"(pixel-weighted and evaluated on {r['image_count']} ")
 
         lines = []
