@@ -203,7 +203,8 @@ typedef struct {
     const float *background;                        /* device: 3 */
     const float *gt;                                /* (3, H, W) */
     const float *alpha_mask;                        /* (H, W) or NULL */
-    const float *mono_invdepth, *depth_mask;        /* (H, W) or NULL (no depth term); mask NULL = ones */
+    const float *mono_invdepth, *depth_mask;        /* (H, W) or NULL (no depth term); mask NULL = ones;
+                                                     * 16-byte aligned (GSR_ERR_INVALID_ARGUMENT otherwise) */
     float depth_weight;                             /* depth_l1_weight(iteration); <= 0: no depth term */
     double lambda_dssim;
     /* densification statistics (P) */

@@ -179,6 +179,10 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
     if (depth_only && (!a->mono_invdepth || !(a->depth_weight > 0.f)))
         return invalid("a depth-only view needs its inverse-depth map and a positive depth weight "
                        "(train_single.py:158-161 has no loss otherwise)");
+    // the depth loss kernels read the maps as float4 (gsr_depth_l1_forward's requirement)
+    if (a->mono_invdepth &&
+        ((reinterpret_cast<uintptr_t>(a->mono_invdepth) | reinterpret_cast<uintptr_t>(a->depth_mask)) & 15u) != 0)
+        return invalid("mono_invdepth and depth_mask must be 16-byte aligned");
     if (depth_only && !(a->depth_dens_weight >= 0.0 && a->depth_dens_weight <= 1.0))
         return invalid("depth_dens_weight outside [0, 1]");
     if (!a->max_radii2D || !a->xyz_gradient_accum || !a->denom) return invalid("NULL densification statistics");

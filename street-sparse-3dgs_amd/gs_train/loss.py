@@ -119,6 +119,16 @@ def photo_loss(img: torch.Tensor, gt: torch.Tensor, lambda_dssim: float = 0.2):
     return (1.0 - lambda_dssim) * l1 + lambda_dssim * (1.0 - s), l1, s
 
 
+def _aligned(t):
+    """float32, contiguous and 16-byte aligned, as the depth loss kernels read their arrays (float4):
+    a contiguous slice of a stacked (V, 1, H, W) tensor starts off such a boundary when H * W is not
+    a multiple of 4, and is copied."""
+    if t is None:
+        return None
+    t = t.detach().float().contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 class _DepthL1(torch.autograd.Function):
     """w * mean(|(invdepth - mono) * mask|) as one node (include/gsr_train.h gsr_depth_l1_*):
     train_single.py:138-140's Ll1depth.  The gradient w.r.t. invdepth is bit-identical to torch's
@@ -130,9 +140,7 @@ class _DepthL1(torch.autograd.Function):
         require_gpu(invd, mono, mask)
         if invd.shape != mono.shape or (mask is not None and mask.shape != invd.shape):
             raise ValueError("invdepth, mono_invdepth and depth_mask must have one shape")
-        x = invd.detach().float().contiguous()
-        y = mono.detach().float().contiguous()
-        m = mask.detach().float().contiguous() if mask is not None else None
+        x, y, m = _aligned(invd), _aligned(mono), _aligned(mask)
         n = x.numel()
         L = lib()
         out = torch.empty(2, dtype=torch.float32, device=x.device)
@@ -175,9 +183,7 @@ class _DepthOnlyLoss(torch.autograd.Function):
         require_gpu(invd, mono, mask)
         if invd.shape != mono.shape or (mask is not None and mask.shape != invd.shape):
             raise ValueError("invdepth, mono_invdepth and depth_mask must have one shape")
-        x = invd.detach().float().contiguous()
-        y = mono.detach().float().contiguous()
-        m = mask.detach().float().contiguous() if mask is not None else None
+        x, y, m = _aligned(invd), _aligned(mono), _aligned(mask)
         n = x.numel()
         L = lib()
         out = torch.empty(3, dtype=torch.float32, device=x.device)

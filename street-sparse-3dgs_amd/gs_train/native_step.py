@@ -38,6 +38,7 @@ class NativeTrainStep(TrainStep):
         super().__init__(*args, **kw)
         self._ctx = None
         self._key = None
+        self._copies = {}
         ctx = lib().gsr_train_ctx_create()
         if not ctx:
             raise RuntimeError("gsr_train_ctx_create failed")
@@ -141,6 +142,19 @@ class NativeTrainStep(TrainStep):
             (g._exposure.data_ptr(), g.max_radii2D.data_ptr(), g.xyz_gradient_accum.data_ptr(), g.denom.data_ptr(),
              g.active_sh_degree) + moments
 
+    def _aligned(self, kind, k, t):
+        """View k's depth map or mask as gsr_train_step needs it: 16-byte aligned (its depth loss
+        kernels load float4).  A slice of a stacked (V, 1, H, W) tensor starts off such a boundary
+        when H * W is not a multiple of 4; it is copied once and the copy kept while the tensor
+        stays the same object and version (the maps are constants of the problem)."""
+        if t.data_ptr() % 16 == 0:
+            return t
+        hit = self._copies.get((kind, k))
+        if hit is None or hit[0] is not t or hit[1] != t._version:
+            hit = (t, t._version, t.clone())
+            self._copies[(kind, k)] = hit
+        return hit[2]
+
     @staticmethod
     def _advance(entries, carr):
         """Adam.step's bookkeeping: one step per parameter, bias corrections in double."""
@@ -193,9 +207,9 @@ class NativeTrainStep(TrainStep):
         depth = mono is not None and w > 0
         if depth_only and not depth:
             raise ValueError("a depth-only iteration with no depth weight has no loss (train_single.py:158-161)")
-        a.mono_invdepth = mono.data_ptr() if depth else None
+        a.mono_invdepth = self._aligned("mono", k, mono).data_ptr() if depth else None
         dm = self.dmask[k]
-        a.depth_mask = dm.data_ptr() if (depth and dm is not None) else None
+        a.depth_mask = self._aligned("mask", k, dm).data_ptr() if (depth and dm is not None) else None
         a.depth_weight = w if depth else 0.0
         a.depth_only = int(depth_only)
         a.depth_dens_weight = self.dens_weight

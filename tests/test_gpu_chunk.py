@@ -89,7 +89,15 @@ def test_native_step_with_depth_only_views_equals_python_step_steep_poses():
                                        world=PC.steep_world(20_000, 256, 192, 1))
 
 
-def _native_step_with_depth_only_views(skybox, alpha, n_views, depth_only, steps, photometric_steps, world=None):
+def test_native_step_with_depth_only_views_equals_python_step_ragged_frame():
+    """The same view cycle at 251 x 189: H * W is odd, so the depth-only forward with its gradient
+    ends in the scalar tail, and no side is a multiple of the SSIM strips."""
+    _native_step_with_depth_only_views(300, True, n_views=5, depth_only=2, steps=7, photometric_steps=5.0,
+                                       size=(251, 189))
+
+
+def _native_step_with_depth_only_views(skybox, alpha, n_views, depth_only, steps, photometric_steps, world=None,
+                                       size=(256, 192)):
     from helpers import deterministic
     from gs_train.harness import make_problem
     from gs_train.native_step import NativeTrainStep
@@ -97,7 +105,7 @@ def _native_step_with_depth_only_views(skybox, alpha, n_views, depth_only, steps
     with deterministic():
         for native in (False, True):
             torch.manual_seed(0)
-            ts = make_problem(20_000, 256, 192, n_views=n_views, seed=1, step_cls=NativeTrainStep if native else None,
+            ts = make_problem(20_000, *size, n_views=n_views, seed=1, step_cls=NativeTrainStep if native else None,
                               depth=True, alpha=alpha, skybox_points=skybox, depth_only=depth_only, world=world)
             torch.manual_seed(3)
             losses = torch.stack([ts.step().clone() for _ in range(steps)])

@@ -242,6 +242,16 @@ def test_train_step_fused_matches_reference_structured_step(depth, alpha, skybox
     """The fused Street-sparse iteration against the reference's torch formulation of it
     (oracle/train_torch_ref.ReferenceTrainStep): with and without the masked inverse-depth L1,
     the alpha mask and a locked skybox."""
+    _train_step_fused_matches_reference_structured_step(depth, alpha, skybox, scaffold)
+
+
+def test_train_step_fused_matches_reference_structured_step_ragged_frame():
+    """The same at 251 x 189 with depth, alpha and a skybox: neither side a multiple of the 64-wide
+    SSIM strips, H * W odd (every float4 pass ends in a scalar tail)."""
+    _train_step_fused_matches_reference_structured_step(True, True, 300, 0, size=(251, 189))
+
+
+def _train_step_fused_matches_reference_structured_step(depth, alpha, skybox, scaffold, size=(256, 192)):
     from gs_train.harness import LR, make_problem
     from helpers import assert_adam_trajectories_close, record_margins
     from train_torch_ref import ReferenceTrainStep
@@ -249,7 +259,7 @@ def test_train_step_fused_matches_reference_structured_step(depth, alpha, skybox
     steps, n_steps = {}, 3
     for fused in (True, False):
         torch.manual_seed(0)
-        ts = make_problem(20_000, 256, 192, n_views=3, seed=1, step_cls=None if fused else ReferenceTrainStep,
+        ts = make_problem(20_000, *size, n_views=3, seed=1, step_cls=None if fused else ReferenceTrainStep,
                           depth=depth, alpha=alpha, skybox_points=skybox, scaffold_points=scaffold)
         if scaffold:  # some over-large Gaussians on both sides of the scaffold boundary: the shrink runs
             with torch.no_grad():
@@ -269,7 +279,8 @@ def test_train_step_fused_matches_reference_structured_step(depth, alpha, skybox
                _rotation=LR["rotation_lr"])
     for n, x, y, x0 in zip(names, pa, pb, ia):
         worst, close = assert_adam_trajectories_close(n, x, y, x0, lrs[n], n_steps, atol=1e-5)
-        record_margins(f"fused_vs_reference_step_{depth}_{alpha}_{skybox}_{scaffold}{n}", travel_frac=worst,
+        tag = "" if size == (256, 192) else f"_{size[0]}x{size[1]}"
+        record_margins(f"fused_vs_reference_step_{depth}_{alpha}_{skybox}_{scaffold}{tag}{n}", travel_frac=worst,
                        close=close)
     assert torch.equal(da, db)
     assert torch.isclose(aa, ab, rtol=1e-3, atol=1e-9).float().mean().item() >= 0.999
@@ -301,7 +312,43 @@ def test_native_step_equals_python_step_steep_poses():
     _native_step_equals_python_step(True, True, 300, 0, n_views=2, world=PC.steep_world(20_000, 256, 192, 1))
 
 
-def _native_step_equals_python_step(depth, alpha, skybox, scaffold, n_views, world=None):
+@pytest.mark.parametrize("size", [(251, 189), (643, 409)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_native_step_equals_python_step_ragged_frames(size):
+    """The same with depth, alpha and a skybox at 251 x 189 and 643 x 409: no side a multiple of
+    the 64-wide SSIM strips, H * W odd (the float4 depth pass ends in its scalar tail) and, at
+    262,987 px, above the exposure grid's cap (a second grid-stride trip) -- the edges of the
+    variants fused into the native step (the SSIM pass that writes the photometric gradient, the
+    exposure backward that forms it, the depth forward with its gradient, the fused finalizes)."""
+    _native_step_equals_python_step(True, True, 300, 0, n_views=3, size=size)
+
+
+def test_native_step_equals_python_step_on_slices_of_stacked_views():
+    """At 251 x 189 with every view's gt, mono map, depth mask and alpha mask a slice of one stacked
+    tensor: H * W is odd, so the slices of views 1 and 2 start off a 16-byte boundary.  Each alpha
+    mask has a zero block over which gt is zero too (masked sky: img == gt, sgn(0) = 0); gt is zero
+    on a strip beside it as well, and view 1's exposure is the zero matrix, so that its image is
+    exactly 0 from pre-clamp values of exactly 0 (the clamp passes the gradient): on that strip
+    img == gt under a nonzero alpha, and a wrong sgn(0) reaches the exposure gradient.  The native
+    step copies the misaligned depth maps (gsr_train_step refuses them; gt and alpha are read by
+    scalar loads) and stays bit-identical to the Python-driven step."""
+    _native_step_equals_python_step(True, True, 300, 0, n_views=3, size=(251, 189), stacked=True)
+
+
+def _stack_views(ts):
+    """The step's per-view constants as slices of one stacked tensor each, with a masked-sky block."""
+    gts, alphas = torch.stack(ts.gts), torch.stack(ts.amask)
+    alphas[:, :, 20:60, 30:90] = 0.0
+    gts[:, :, 20:60, 30:120] = 0.0
+    with torch.no_grad():
+        ts.g._exposure[1].zero_()
+    ts.gts, ts.amask = list(gts.unbind(0)), list(alphas.unbind(0))
+    ts.mono, ts.dmask = list(torch.stack(ts.mono).unbind(0)), list(torch.stack(ts.dmask).unbind(0))
+    for maps in (ts.gts, ts.amask, ts.mono, ts.dmask):
+        assert maps[1].data_ptr() % 16 != 0 and maps[1].is_contiguous()
+
+
+def _native_step_equals_python_step(depth, alpha, skybox, scaffold, n_views, world=None, size=(256, 192),
+                                    stacked=False):
     from helpers import deterministic
     from gs_train.harness import make_problem
     from gs_train.native_step import NativeTrainStep
@@ -310,8 +357,10 @@ def _native_step_equals_python_step(depth, alpha, skybox, scaffold, n_views, wor
     with deterministic():
         for native in (False, True):
             torch.manual_seed(0)
-            ts = make_problem(20_000, 256, 192, n_views=n_views, seed=1, step_cls=NativeTrainStep if native else None,
+            ts = make_problem(20_000, *size, n_views=n_views, seed=1, step_cls=NativeTrainStep if native else None,
                               depth=depth, alpha=alpha, skybox_points=skybox, scaffold_points=scaffold, world=world)
+            if stacked:
+                _stack_views(ts)
             if scaffold:
                 with torch.no_grad():
                     ts.g._scaling[scaffold - 50:scaffold + 50] += 3.0

@@ -231,3 +231,81 @@ def test_spatial_reorder_is_a_row_permutation():
     pts = torch.cat((torch.full((5, 3), 1.0), torch.full((5, 3), -1.0), torch.full((5, 3), 1.0)))
     o = spatial_order(pts)
     assert o.tolist() == [5, 6, 7, 8, 9, 0, 1, 2, 3, 4, 10, 11, 12, 13, 14]
+
+
+def _edge_cases():
+    import train_edge_cases as EC
+    return EC
+
+
+@pytest.mark.parametrize("case", _edge_cases().SSIM_CASES)
+def test_edge_inputs_are_well_conditioned(case):
+    """The ragged-size, out-of-range and tie inputs of tests/test_gpu_train_edges.py: the fp32 torch
+    reference itself sits within a quarter of each bar the kernels are held to against fp64 (values
+    2e-6, gradient 1e-5 of max|grad|), so a case that the reference alone cannot pass is never
+    offered to a kernel.  (The flat planes are ill-conditioned in fp32 and carry their own bars.)"""
+    EC = _edge_cases()
+    img, gt, tie = EC.ssim_inputs(case)
+    l1, s, grad = EC.l1_ssim_ref(img, gt)
+    l1f, sf, gradf = EC.l1_ssim_ref(img, gt, dtype=torch.float32)
+    assert abs(l1f - l1) <= EC.VALUE_BAR / 4 and abs(sf - s) <= EC.VALUE_BAR / 4
+    assert (gradf.double() - grad).abs().max().item() <= EC.GRAD_BAR / 4 * grad.abs().max().item()
+    if tie is not None:  # sgn(0) = 0: the L1 part of the gradient vanishes on the ties
+        assert bool((EC.l1_ssim_ref(img, gt, up=(1.0, 0.0))[2][tie] == 0).all())
+
+
+def test_edge_exposure_and_image_side_inputs_keep_off_the_clamp_edges():
+    """The exposure inputs keep every pre-clamp value 1e-5 clear of 0 and 1 (fp32 and fp64 clamp
+    alike), an fp32 torch evaluation then sits well inside the bars, and the tie inputs hold each of
+    the five colours with exact pre-clamp values."""
+    EC = _edge_cases()
+    for H, W in EC.EXPOSURE_SIZES[:3] + [(5, 52429)]:
+        for localised in (False, True):
+            color, E, up = EC.exposure_inputs(H, W, localised)
+            pre = EC.exposure_pre(color.double(), E.double())
+            assert torch.minimum(pre.abs(), (pre - 1).abs()).min().item() >= EC.CLAMP_MARGIN
+            out, dc, dE, terms = EC.exposure_ref(color, E, up)
+            outf, dcf, dEf, _ = EC.exposure_ref(color, E, up, dtype=torch.float32)
+            assert (outf.double() - out).abs().max().item() <= 5e-7
+            assert (dcf.double() - dc).abs().max().item() <= 5e-7
+            assert bool(((dEf.double() - dE).abs() <= EC.EXPOSURE_DE_BOUND / 4 * terms).all())
+            if localised and H * W > 303:
+                assert int((up != 0).any(dim=0).sum()) <= 303
+    color, E, up = EC.exposure_tie_inputs(1, 257)
+    assert torch.equal(EC.exposure_pre(color, E), color)
+    for v in EC.TIE_COLOURS:
+        assert bool((color == v).any())
+    p = EC.image_side_inputs(*EC.IMAGE_SIDE_SIZES[0])
+    loss, dc, di, dE, terms = EC.image_side_ref(p)
+    lossf, dcf, dif, dEf, _ = EC.image_side_ref(p, dtype=torch.float32)
+    assert abs(lossf - loss) <= EC.VALUE_BAR / 4
+    assert (dcf.double() - dc).abs().max().item() <= EC.GRAD_BAR / 4 * dc.abs().max().item()
+    assert torch.equal(dif.double() * 0 + dif.sign().double(), di.sign())
+    assert bool(((dEf.double() - dE).abs() <= EC.EXPOSURE_DE_BOUND / 4 * terms).all())
+
+
+def test_depth_loss_operands_off_a_16_byte_boundary_are_copied():
+    """The depth loss kernels load float4: the wrappers (gs_train.loss._aligned) and the native step
+    (NativeTrainStep._aligned) hand them a copy of a contiguous slice that starts off a 16-byte
+    boundary, and the tensor itself otherwise; the native step keeps its copy while the map is
+    unchanged."""
+    from gs_train.loss import _aligned
+    from gs_train.native_step import NativeTrainStep
+    stack = torch.arange(3 * 37 * 53, dtype=torch.float32).reshape(3, 1, 37, 53)
+    assert _aligned(None) is None
+    assert _aligned(stack[0]).data_ptr() == stack[0].data_ptr()
+    step = NativeTrainStep.__new__(NativeTrainStep)
+    step._copies = {}
+    step._ctx = None
+    for k in (1, 2):
+        t = stack[k]
+        assert t.is_contiguous() and t.data_ptr() % 16 != 0
+        for c in (_aligned(t), step._aligned("mono", k, t)):
+            assert c.data_ptr() % 16 == 0 and torch.equal(c, t)
+        assert step._aligned("mono", k, t) is step._aligned("mono", k, t)
+        kept = step._aligned("mono", k, t)
+        t += 1.0  # a new version of the map: the kept copy is stale
+        fresh = step._aligned("mono", k, t)
+        assert fresh is not kept and torch.equal(fresh, t)
+    first = stack[0]
+    assert step._aligned("mask", 0, first) is first
