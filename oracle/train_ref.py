@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY -- CPU restatement of the train-step pieces around the rasterizer.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module; the
-product (street-sparse-3dgs_amd/gs_train) runs the gfx950 kernels in csrc/train.hip and never
+product (street-sparse-3dgs_amd/gs_train) runs the gfx950 kernels in csrc/loss.hip / optim.hip and never
 touches it.  Pinned against tests/golden/{loss,adam,densify}.npz, which
 tests/golden/make_train_golden.py produced by running the reference's own functions.
 

@@ -793,7 +793,7 @@ __device__ __forceinline__ void live_row(int i, const Mat4 &V, int D, const floa
     float ds[3], dq[4];
     scale_rot_chain(q, s_in, mod, dscale_mod, dcov, ds, dq);
     if (act.on) {
-        // the activation backward (train.hip activate_bwd_step_kernel's expressions): exp,
+        // the activation backward (optim.hip activate_bwd_step_kernel's expressions): exp,
         // normalise and sigmoid with the skybox lock, the densification statistics and the
         // relevance flag of this live row
 #pragma unroll

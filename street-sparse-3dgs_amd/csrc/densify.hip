@@ -257,12 +257,7 @@ static int densify_plan(const char *who, int64_t P0, int64_t first_row, const fl
     hipLaunchKernelGGL(densify_totals_kernel, dim3(1), dim3(64), 0, s, P0, L.flags, L.pre, L.tot, counts);
     if (P0 > 0)
         hipLaunchKernelGGL(densify_map_kernel, dim3(blocks), dim3(256), 0, s, P0, L.flags, L.pre, L.tot, L.map);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string(who) + ": " + hipGetErrorString(e));
-        return GSR_ERR_DEVICE;
-    }
-    return GSR_OK;
+    return launched(who);
 }
 
 int gsr_densify_plan(int64_t P0, int64_t first_row, const float *grad_accum, const float *max_radii2D,
@@ -328,12 +323,7 @@ int gsr_densify_apply(int64_t P0, int n_groups, const gsr_row_group *src, const 
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(densify_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, L.map, normals, n_split,
                        total_rows);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string("gsr_densify_apply: ") + hipGetErrorString(e));
-        return GSR_ERR_DEVICE;
-    }
-    return GSR_OK;
+    return launched("gsr_densify_apply");
 }
 
 }  // extern "C"

@@ -336,15 +336,6 @@ dim3 eval_grid(int H, int W) { return dim3((W + kTW - 1) / kTW, (H + kTH - 1) / 
 
 unsigned stride_blocks(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 4096); }
 
-int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-        return GSR_ERR_DEVICE;
-    }
-    return GSR_OK;
-}
-
 bool bad_bits(int n, int shift) { return n < 0 || shift < 0 || shift + n > GSR_EVAL_MAX_REGIONS; }
 
 }  // namespace

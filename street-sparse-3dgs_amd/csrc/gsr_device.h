@@ -165,7 +165,7 @@ __device__ __forceinline__ void cut_source(const CutRef &c, int64_t r, int64_t &
 }
 
 // Parameter activations (scene/gaussian_model.py:39-47, getters :125-156), in torch's op order:
-// exp, x / max(||x||, 1e-12), sigmoid.  train.hip's activate kernels and the raw-parameter mode of
+// exp, x / max(||x||, 1e-12), sigmoid.  optim.hip's activate kernels and the raw-parameter mode of
 // the rasterizer (GaussianInputs.raw: the native train step) use these, so both form the same bits.
 __device__ __forceinline__ float act_scale(float s) { return expf(s); }
 __device__ __forceinline__ float4 act_rot(float4 q) {

@@ -11,6 +11,9 @@ namespace gsr {
 
 // rasterizer.hip: message returned by gsr_last_error() for the calling thread.
 void set_last_error(const std::string &msg);
+// The end of a function that launched kernels: GSR_OK, or hipGetLastError()'s error as
+// "<who>: <its text>" in the thread's message and GSR_ERR_DEVICE (the message is built on failure only).
+int launched(const char *who);
 // gsr_set_true_scale_gradient: dL/dscales including the scale_modifier factor (default off: upstream)
 bool true_scale_gradient();
 
@@ -227,48 +230,103 @@ struct BackwardCall {
     decltype(gsr_rasterize_backward) run;
 };
 
-// train.hip: the native train step's fused launches (train_step.hip).  sparse_adam is
-// gsr_sparse_adam_step (flag_ready: the relevance flag is already computed; shrink_raw != NULL:
-// train_single.py:235-241's scale shrink of rows >= shrink_first in the same launch).
-// live3 != NULL (sparse gradient rows): when no row is relevant, the dense fallback takes a zero
-// gradient for rows whose live3[3 row + 2] is 0 (never written) and for the locked skybox rows
-// below `skybox` (train_single.py:217-223 zeroes all six of their gradients).
-// row_list: scratch of >= P + 64 ints for the compacted row list (the train context's grow-only
-// slot); NULL: allocated per call in stream order, and the row-block kernel (no scratch) runs when
-// that allocation fails.
-int sparse_adam(int n_groups, const gsr_adam_group *groups, int64_t P, const float *relevance, double beta1,
-                double beta2, double eps, int *flag_scratch, bool flag_ready, hipStream_t s, float *shrink_raw,
-                int64_t shrink_first, float shrink_limit, const float *live3 = nullptr, int64_t skybox = 0,
-                int *row_list = nullptr);
-// SSIM map forward (+ masked inverse-depth L1 forward with its gradient for an upstream of 1 when
-// mono != NULL) and the loss epilogue: losses[0..2] photometric, [3..4] depth, [5] total; *flag = 0.
-// one != NULL: gmap receives the photometric gradient itself (dL/dloss = *one, times alpha when
-// given), and *gmap_is_photo says so (the streaming SSIM kernel; the tile kernel writes G)
-int step_loss_forward(const float *img, const float *gt, int H, int W, double lambda_dssim, void *loss_scratch,
-                      float *gmap, const float *invd, const float *mono, const float *mask, float depth_w,
-                      void *depth_scratch, float *d_invd, float *losses, int *flag, hipStream_t s,
-                      const float *one = nullptr, const float *alpha = nullptr, bool *gmap_is_photo = nullptr);
-// the depth-only view's loss (gsr_depth_only_loss) with its gradient for an upstream of 1 in d_invd;
+// loss.hip (the image side) and optim.hip (the Gaussian side): the native train step's fused
+// launches (train_step.hip).  What a launch works on is passed as one struct per term of the step,
+// filled by member name in gsr_train_step.
+
+// torch applies these python floats as fp32 scalars: b and (1 - b) are rounded from the double
+struct AdamHyper {
+    double beta1, beta2, eps;
+};
+
+// The photometric term (train_single.py:121-123) of one view, shared by step_loss_forward and
+// step_loss_backward.
+struct PhotoTerms {
+    const float *img;  // (3, H, W): the exposed image (x the alpha mask)
+    const float *gt;   // (3, H, W): the target
+    int H, W;
+    double lambda_dssim;
+    const float *one;    // device: dL/dloss (1)
+    const float *alpha;  // (H, W) or NULL
+    // (3, H, W), written by the forward: the SSIM gradient field G (the tile kernel), or the
+    // photometric gradient itself (dL/dloss = *one, times alpha when given; the streaming kernel).
+    // gmap_is_photo says which: the forward sets it, the backward reads it.
+    float *gmap;
+    bool gmap_is_photo = false;
+};
+
+// The masked inverse-depth L1 (train_single.py:135-141), or the depth-only view's loss
+// (gsr_depth_only_loss), with its gradient for an upstream of 1 in d_invd.
+struct DepthTerms {
+    const float *invd;  // rendered
+    const float *mono;  // target; NULL: no depth term
+    const float *mask;  // or NULL
+    float weight;
+    void *scratch;  // gsr_depth_l1_scratch_bytes / gsr_depth_only_scratch_bytes
+    float *d_invd;
+};
+
+// The view's exposure: colour -> exposed image (launch_exposure_forward: color, E, npix), and in
+// step_loss_backward the colour gradient, the exposure gradient and the exposure optimizer's step.
+struct ExposureTerms {
+    const float *color;  // rendered (3, H, W)
+    const float *E;      // the view's 3 x 4 (row `view` of the group's n_images x 12 parameter)
+    int64_t npix;
+    float *d_color;
+    void *scratch;  // gsr_exposure_scratch_bytes
+    int n_images, view;
+    gsr_adam_group group;
+    float *grad;  // n_images x 12
+    AdamHyper adam;
+};
+
+// What the native step adds to gsr_sparse_adam_step (the defaults: that entry point as it is).
+struct SparseAdamOpts {
+    bool flag_ready = false;  // the relevance flag is already computed: no any-nonzero pass
+    // train_single.py:235-241's scale shrink of rows >= shrink_first in the same launch (NULL: none)
+    float *shrink_raw = nullptr;
+    int64_t shrink_first = 0;
+    float shrink_limit = 0.f;
+    // live3 != NULL (sparse gradient rows): when no row is relevant, the dense fallback takes a zero
+    // gradient for rows whose live3[3 row + 2] is 0 (never written) and for the locked skybox rows
+    // below `skybox` (train_single.py:217-223 zeroes all six of their gradients).
+    const float *live3 = nullptr;
+    int64_t skybox = 0;
+    // scratch of >= P + 64 ints for the compacted row list (the train context's grow-only slot);
+    // NULL: allocated per call in stream order, and the row-block kernel (no scratch) runs when
+    // that allocation fails.
+    int *row_list = nullptr;
+};
+int sparse_adam(int n_groups, const gsr_adam_group *groups, int64_t P, const float *relevance, int *flag_scratch,
+                const AdamHyper &hyper, const SparseAdamOpts &opts, hipStream_t s);
+
+// SSIM map forward (+ the depth term's forward with its gradient when depth.mono != NULL) and the
+// loss epilogue: losses[0..2] photometric, [3..4] depth, [5] total; *flag = 0.
+int step_loss_forward(PhotoTerms &photo, const DepthTerms &depth, void *loss_scratch, float *losses, int *flag,
+                      hipStream_t s);
+// the depth-only view's loss over n pixels (dens_weight: additional_depth_maps_weight);
 // losses = (dens, 0, 0, pure, loss, loss); *flag = 0
-int step_depth_only_forward(const float *invd, const float *mono, const float *mask, int64_t n, float w, double a,
-                            void *depth_scratch, float *d_invd, float *losses, int *flag, hipStream_t s);
-int launch_exposure_forward(const float *color, const float *E, int64_t npix, float *out, const float *alpha,
+int step_depth_only_forward(const DepthTerms &depth, int64_t n, double dens_weight, float *losses, int *flag,
                             hipStream_t s);
+int launch_exposure_forward(const ExposureTerms &exposure, float *out, const float *alpha, hipStream_t s);
 // photometric gradient (x alpha) through the exposure into d_color, the exposure gradient and the
 // exposure optimizer's dense Adam step
-int step_loss_backward(const float *img, const float *gt, const float *gmap, const float *one, double lambda_dssim,
-                       const float *alpha, const float *color, const float *E_view, int64_t npix, float *d_color,
-                       void *exp_scratch, int n_images, int view, const gsr_adam_group &eg, float *exposure_grad,
-                       double b1, double b2, double eps, hipStream_t s, bool gmap_is_photo = false);
-// activation backward + skybox lock + relevance flag + densification statistics.  sparse_rows:
-// the rasterizer backward wrote sparse rows (GaussianGrads): the scale / rotation gradients of
-// rows it did not write are neither read nor written.  The activations are recomputed from the raw
-// parameters (rotation_raw, scaling_raw, opacity_raw).
-int step_activate_backward(int64_t P, const float *rotation_raw, const float *d_scales, const float *d_rots,
-                           const float *d_opac, float *scaling_grad, float *rotation_grad, float *opacity_grad,
-                           int64_t skybox, int *flag, const int *radii, const float *d_means2D, float *max_radii2D,
-                           float *accum, float *denom, hipStream_t s, bool sparse_rows, const float *scaling_raw,
-                           const float *opacity_raw);
+int step_loss_backward(const PhotoTerms &photo, const ExposureTerms &exposure, hipStream_t s);
+
+// What step_activate_backward takes beside the StepAct the fused form takes: the rasterizer
+// backward's gradients of the activated parameters, the raw parameters' gradients it writes, and
+// the screen-space gradient.  sparse_rows: the rasterizer backward wrote sparse rows
+// (GaussianGrads): the scale / rotation gradients of rows it did not write are neither read nor
+// written.
+struct ActGrads {
+    const float *d_scales, *d_rots, *d_opac;
+    float *scaling_grad, *rotation_grad, *opacity_grad;
+    const float *d_means2D;
+    bool sparse_rows;
+};
+// activation backward + skybox lock + relevance flag + densification statistics, the activations
+// recomputed from the raw parameters (act.s_raw, q_raw, o_raw)
+int step_activate_backward(int64_t P, const StepAct &act, const ActGrads &grads, hipStream_t s);
 
 // kernel stamps of each translation unit (GSR_KSTAMP builds; gsr_kstamp_read)
 int kstamp_read_preprocess(unsigned long long *out);

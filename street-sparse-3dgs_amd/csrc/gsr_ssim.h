@@ -1,5 +1,5 @@
 // gsr_ssim.h -- the 11x11 Gaussian window of SSIM (utils/loss_utils.py:23-58) as the LDS-tiled
-// separable passes share it: train.hip (the loss) and eval.hip (the evaluation metrics).  A 64x16
+// separable passes share it: loss.hip (the loss) and eval.hip (the evaluation metrics).  A 64x16
 // output tile per 256-thread workgroup; the horizontal pass writes the five windowed moments of a
 // staged halo, the vertical pass finishes them for four rows per thread.
 #pragma once

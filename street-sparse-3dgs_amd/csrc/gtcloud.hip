@@ -438,12 +438,7 @@ int gsr_gt_far_mask(int64_t P, const float *xyz, const gsr_gt_index *index, doub
         return GSR_ERR_INVALID_ARGUMENT;
     }
     launch_gt_far_mask(P, xyz, g, T, reach, skip, out_mask, static_cast<hipStream_t>(stream));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string("gsr_gt_far_mask: ") + hipGetErrorString(e));
-        return GSR_ERR_DEVICE;
-    }
-    return GSR_OK;
+    return launched("gsr_gt_far_mask");
 }
 
 }  // extern "C"

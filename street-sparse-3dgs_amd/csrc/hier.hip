@@ -358,12 +358,7 @@ int cut_forward(int64_t N, int M, int64_t R, int64_t S, const int *render_indice
                        static_cast<hipStream_t>(stream), N, M, R, S, render_indices, parent_indices,
                        interpolation_weights, means3D, scales, rotations, opacities, shs, out_means3D, out_scales,
                        out_rotations, out_opacities, out_shs, vec, act);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string(who) + ": " + hipGetErrorString(e));
-        return GSR_ERR_DEVICE;
-    }
-    return GSR_OK;
+    return launched(who);
 }
 
 int cut_backward(int64_t N, int M, int64_t R, int64_t S, const int *render_indices, const int *parent_indices,
@@ -401,12 +396,7 @@ int cut_backward(int64_t N, int M, int64_t R, int64_t S, const int *render_indic
                            dim3(256), 0,
                            static_cast<hipStream_t>(stream), N, R, S, render_indices, parent_indices,
                            interpolation_weights, dL_dout_shs, dL_dshs, uniq);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string(who) + ": " + hipGetErrorString(e));
-        return GSR_ERR_DEVICE;
-    }
-    return GSR_OK;
+    return launched(who);
 }
 
 constexpr int kZeroMax = 8;
@@ -509,12 +499,7 @@ int gsr_zero_grad_rows(int n, float *const *grads, const int64_t *widths, int64_
     if (m == 0 || n == 0) return GSR_OK;
     hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)n), dim3(256), 0,
                        static_cast<hipStream_t>(stream), z, n, N, tail, rows, n_rows);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string("gsr_zero_grad_rows: ") + hipGetErrorString(e));
-        return GSR_ERR_DEVICE;
-    }
-    return GSR_OK;
+    return launched("gsr_zero_grad_rows");
 }
 
 }  // extern "C"

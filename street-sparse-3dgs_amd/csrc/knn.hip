@@ -290,7 +290,7 @@ int gsr_knn_mean_dist2(int64_t N, const float *points, float *out, void *scratch
     const int64_t gb = (N + 255) / 256;
     hipLaunchKernelGGL(knn_bbox_kernel, dim3((unsigned)(gb < 2048 ? gb : 2048)), dim3(256), 0, s, N, points, L.bb);
     hipLaunchKernelGGL(knn_morton_kernel, dim3((unsigned)gb), dim3(256), 0, s, N, points, L.bb, L.key, L.idx);
-    hipError_t e = sort_pairs(L.tmp, L.tmp_bytes, L.key, L.key_s, L.idx, L.idx_s, (size_t)N, 30, s);
+    const hipError_t e = sort_pairs(L.tmp, L.tmp_bytes, L.key, L.key_s, L.idx, L.idx_s, (size_t)N, 30, s);
     if (e != hipSuccess) {
         set_last_error(std::string("gsr_knn_mean_dist2: sort: ") + hipGetErrorString(e));
         return GSR_ERR_DEVICE;
@@ -301,12 +301,7 @@ int gsr_knn_mean_dist2(int64_t N, const float *points, float *out, void *scratch
                        dim3(64 * kKnnWaves), 0, s, L.boxes, nb, L.sboxes, nsb);
     hipLaunchKernelGGL(knn_query_kernel, dim3((unsigned)((nb + kKnnWaves - 1) / kKnnWaves)), dim3(64 * kKnnWaves), 0,
                        s, N, L.pts, L.boxes, nb, L.sboxes, nsb, L.idx_s, out);
-    e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string("gsr_knn_mean_dist2: ") + hipGetErrorString(e));
-        return GSR_ERR_DEVICE;
-    }
-    return GSR_OK;
+    return launched("gsr_knn_mean_dist2");
 }
 
 }  // extern "C"

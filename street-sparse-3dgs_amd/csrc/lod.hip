@@ -406,10 +406,7 @@ int gsr_interpolation_weights(int64_t n, const int *node_indices, float target_s
     hipLaunchKernelGGL(lod_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), n, node_indices, target_size, nodes, boxes, vx, vy, vz,
                        weights, num_kids);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail_lod(GSR_ERR_DEVICE, std::string("gsr_interpolation_weights: ") + hipGetErrorString(e));
-    return GSR_OK;
+    return launched("gsr_interpolation_weights");
 }
 
 }  // extern "C"

@@ -295,15 +295,6 @@ int64_t tap_blocks(int h, int w) {
     return (Q + kTapQuads - 1) / kTapQuads;
 }
 
-int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-        return GSR_ERR_DEVICE;
-    }
-    return GSR_OK;
-}
-
 bool bad_regions(int n) { return n < 0 || n > GSR_LPIPS_MAX_REGIONS; }
 
 // The largest workgroup asks for more than the 64 KiB a kernel gets without saying so.

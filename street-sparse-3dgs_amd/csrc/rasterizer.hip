@@ -521,6 +521,15 @@ int validate_common(int P, int D, int M, const float *shs, const float *colors_p
 
 void gsr::set_last_error(const std::string &msg) { g_err = msg; }
 
+int gsr::launched(const char *who) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_last_error(std::string(who) + ": " + hipGetErrorString(e));
+        return GSR_ERR_DEVICE;
+    }
+    return GSR_OK;
+}
+
 namespace {
 std::atomic<int> g_true_scale_grad{0};
 #ifndef GSR_DETERMINISTIC_DEFAULT

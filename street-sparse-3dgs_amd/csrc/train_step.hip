@@ -246,39 +246,54 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
                  a->campos, a->tan_fovx, a->tan_fovy, 0, color, invd, radii, nullptr, nullptr, nullptr, nullptr, 0, 0,
                  sv, &K, 0);
     if (rc) return fail_step(rc, "rasterizer forward");
-    const float *E = a->exposure + 12 * (int64_t)a->image_index;
+    DepthTerms dterms;  // of either kind of view
+    dterms.invd = invd;
+    dterms.mono = depth ? a->mono_invdepth : nullptr;  // a depth-only view always has it (checked above)
+    dterms.mask = a->depth_mask;
+    dterms.weight = a->depth_weight;
+    dterms.scratch = depth_scratch;
+    dterms.d_invd = d_invd;
     if (depth_only) {
         // a depth-only view (train_single.py:145-161): the rendered image is in no loss, so the
         // exposure pass, the SSIM pass and the exposure step (:213-214) do not run; the colour
         // gradient is zero and the exposure gradient is zeroed (:203-209)
-        if ((rc = step_depth_only_forward(invd, a->mono_invdepth, a->depth_mask, npix, a->depth_weight,
-                                          a->depth_dens_weight, depth_scratch, d_invd, a->losses, flag, s)))
+        if ((rc = step_depth_only_forward(dterms, npix, a->depth_dens_weight, a->losses, flag, s)))
             return fail_step(rc, "depth-only loss");
         if (hipMemsetAsync(d_color, 0, sizeof(float) * 3 * npix, s) != hipSuccess ||
             hipMemsetAsync(a->exposure_grad, 0, sizeof(float) * 12 * (size_t)a->n_images, s) != hipSuccess)
             return fail_step(GSR_ERR_DEVICE, "depth-only zero gradients");
     } else {
+        ExposureTerms exposure;
+        exposure.color = color;
+        exposure.E = a->exposure + 12 * (int64_t)a->image_index;
+        exposure.npix = npix;
+        exposure.d_color = d_color;
+        exposure.scratch = exp_scratch;
+        exposure.n_images = a->n_images;
+        exposure.view = a->image_index;
+        exposure.group = *a->exposure_group;
+        exposure.grad = a->exposure_grad;
+        exposure.adam = AdamHyper{a->exposure_beta1, a->exposure_beta2, a->exposure_eps};
         // exposure (x the alpha mask, train_single.py:117-119, in the same pass)
-        if ((rc = launch_exposure_forward(color, E, npix, image, a->alpha_mask, s)))
-            return fail_step(rc, "exposure");
+        if ((rc = launch_exposure_forward(exposure, image, a->alpha_mask, s))) return fail_step(rc, "exposure");
 
         // losses (train_single.py:121-141): the SSIM map pass with its gradient field, the depth L1
         // with its gradient (the loss is the root: dL/dloss = 1), one epilogue for both values and
         // the total
-        bool photo = false;  // the SSIM pass wrote the photometric gradient itself (gsr_launch.h)
-        if ((rc = step_loss_forward(image, a->gt, H, W, a->lambda_dssim, loss_scratch, gmap, invd,
-                                    depth ? a->mono_invdepth : nullptr, a->depth_mask, a->depth_weight,
-                                    depth_scratch, d_invd, a->losses, flag, s, one,
-                                    a->alpha_mask, &photo)))
-            return fail_step(rc, "losses");
+        PhotoTerms photo;
+        photo.img = image;
+        photo.gt = a->gt;
+        photo.H = H;
+        photo.W = W;
+        photo.lambda_dssim = a->lambda_dssim;
+        photo.one = one;
+        photo.alpha = a->alpha_mask;
+        photo.gmap = gmap;
+        if ((rc = step_loss_forward(photo, dterms, loss_scratch, a->losses, flag, s))) return fail_step(rc, "losses");
 
         // loss.backward(): photometric gradient -> alpha mask -> exposure (colour gradient, exposure
         // gradient and the exposure optimizer's step in the same two launches)
-        gsr_adam_group eg = *a->exposure_group;
-        if ((rc = step_loss_backward(image, a->gt, gmap, one, a->lambda_dssim, a->alpha_mask, color, E, npix, d_color,
-                                     exp_scratch, a->n_images, a->image_index, eg, a->exposure_grad,
-                                     a->exposure_beta1, a->exposure_beta2, a->exposure_eps, s, photo)))
-            return fail_step(rc, "loss backward");
+        if ((rc = step_loss_backward(photo, exposure, s))) return fail_step(rc, "loss backward");
     }
     // sparse gradient rows (gsr_launch.h GaussianGrads): the Gaussians no pixel's backward reached
     // (88% of the bench scene) have zero gradients and are never relevant to the sparse Adam, so
@@ -307,21 +322,32 @@ int gsr_train_step(gsr_train_ctx *ctx, const gsr_train_step_args *a, int64_t *nu
     if (fuse_act != bwd.act_done)
         return invalid("the rasterizer backward did not take the fused activation backward it was given");
     // otherwise the activation backward on its own; then the sparse Adam and the shrink (:225-241)
-    if (!fuse_act &&
-        (rc = step_activate_backward(P, a->rotation, d_scales, d_rots, d_opac, a->scaling_grad, a->rotation_grad,
-                                     a->opacity_grad, a->skybox_rows, flag, radii, d_means2D, a->max_radii2D,
-                                     a->xyz_gradient_accum, a->denom, s, sparse_rows, a->scaling, a->opacity)))
-        return fail_step(rc, "activation backward");
-    if (!a->skip_gaussian_step &&
-        (rc = sparse_adam(a->n_groups, a->groups, P, a->opacity_grad, a->beta1, a->beta2, a->eps, flag, true, s,
-                          a->scaling, a->scaffold_rows, a->max_scale, sparse_rows ? d_means2D : nullptr,
-                          a->skybox_rows, adam_list)))
-        return fail_step(rc, "sparse Adam + shrink");
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string("gsr_train_step: ") + hipGetErrorString(e));
-        return GSR_ERR_DEVICE;
+    if (!fuse_act) {
+        ActGrads grads;
+        grads.d_scales = d_scales;
+        grads.d_rots = d_rots;
+        grads.d_opac = d_opac;
+        grads.scaling_grad = a->scaling_grad;
+        grads.rotation_grad = a->rotation_grad;
+        grads.opacity_grad = a->opacity_grad;
+        grads.d_means2D = d_means2D;
+        grads.sparse_rows = sparse_rows;
+        if ((rc = step_activate_backward(P, act, grads, s))) return fail_step(rc, "activation backward");
     }
+    if (!a->skip_gaussian_step) {
+        SparseAdamOpts opts;
+        opts.flag_ready = true;
+        opts.shrink_raw = a->scaling;
+        opts.shrink_first = a->scaffold_rows;
+        opts.shrink_limit = a->max_scale;
+        opts.live3 = sparse_rows ? d_means2D : nullptr;
+        opts.skybox = a->skybox_rows;
+        opts.row_list = adam_list;
+        if ((rc = sparse_adam(a->n_groups, a->groups, P, a->opacity_grad, flag, AdamHyper{a->beta1, a->beta2, a->eps},
+                              opts, s)))
+            return fail_step(rc, "sparse Adam + shrink");
+    }
+    if ((rc = launched("gsr_train_step"))) return rc;
     if (num_rendered) *num_rendered = K;
     return GSR_OK;
 }

@@ -1,5 +1,5 @@
 """gs_train -- the device work of one Street-sparse-3DGS training iteration around the rasterizer
-(SURVEY.md 8(a) row H, 8(f) rows 1-2), on the gfx950 kernels of csrc/train.hip:
+(SURVEY.md 8(a) row H, 8(f) rows 1-2), on the gfx950 kernels of csrc/loss.hip / optim.hip:
 
   loss.l1_ssim / loss.photo_loss   fused L1 + SSIM forward/backward (utils/loss_utils.py)
   optim.Adam                       fused sparse Adam, drop-in for scene/OurAdam.Adam

@@ -1,4 +1,4 @@
-"""Parameter activations and the per-step scale shrink in one launch each (csrc/train.hip):
+"""Parameter activations and the per-step scale shrink in one launch each (csrc/optim.hip):
 
   activate(scaling, rotation, opacity) -> (exp(scaling), normalize(rotation), sigmoid(opacity))
       the getters of scene/gaussian_model.py:125-156 with the activations of :39-47; the backward

@@ -1,4 +1,4 @@
-"""Densification on the device (csrc/train.hip, csrc/densify.hip).
+"""Densification on the device (csrc/optim.hip, csrc/densify.hip).
 
 add_densification_stats: one launch (train_single.py:193-194 + scene/gaussian_model.py:780-793):
 for Gaussians with radius > 0, max_radii2D = max(max_radii2D, radii), xyz_gradient_accum =

@@ -1,5 +1,5 @@
 """Per-image exposure affine + clamp of render() (gaussian_renderer/__init__.py:115-120) as one
-gfx950 launch each way (csrc/train.hip).  The reference runs a (H*W, 3) x (3, 3) GEMM, a
+gfx950 launch each way (csrc/loss.hip).  The reference runs a (H*W, 3) x (3, 3) GEMM, a
 broadcast add and a clamp, and autograd adds two more GEMMs and a spatial reduction in backward;
 at 1080p that GEMM shape alone costs milliseconds on a BLAS library, while the whole op is a
 ~50 MB streaming pass."""

@@ -18,7 +18,7 @@ Per step, as the reference does it:
      zero_grad(set_to_none=True)
   8. shrink over-large Gaussians (train_single.py:235-241)
 
-Every piece runs on the csrc/train.hip kernels and the step is free of host synchronisation (the
+Every piece runs on the csrc/loss.hip / optim.hip kernels and the step is free of host synchronisation (the
 reference's .item() calls feed only its progress bar).  The reference-structured formulation of
 the same step (conv2d SSIM, OurAdam gather/scatter, ...) lives in oracle/train_torch_ref.py
 (ReferenceTrainStep, test infrastructure and the bench's baseline leg) and overrides the hook

@@ -1,6 +1,6 @@
 """Fused photometric loss: mean |img - gt| and mean SSIM (11x11 Gaussian window, sigma 1.5) in one
 gfx950 launch each way (in training the forward also stores the SSIM gradient field and the
-backward is elementwise) (csrc/train.hip), replacing utils/loss_utils.py:17-18 (l1_loss) and
+backward is elementwise) (csrc/loss.hip), replacing utils/loss_utils.py:17-18 (l1_loss) and
 :33-63 (ssim: five depthwise conv2d + elementwise ops) as combined at train_single.py:121-123.
 
 Gradients flow only to `img` (the rendered image); `gt` is a constant, as in the reference.

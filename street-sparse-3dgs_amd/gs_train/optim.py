@@ -9,7 +9,7 @@ own learning rate, so the DC and rest SH coefficients can live in one (P, 16, 3)
 torch.cat / split per step) and still get f_dc's and f_rest's rates.  `step(relevant)` accepts the reference's
 index tensor; `step(relevance=opacity.grad)` skips the host-synchronising nonzero() and tests
 relevance per row on the device.  Either way all groups are updated by ONE gfx950 launch
-(csrc/train.hip) that reads (param, grad, m, v) and writes (param, m, v) once for the relevant
+(csrc/optim.hip) that reads (param, grad, m, v) and writes (param, m, v) once for the relevant
 rows; with no relevant row every row is updated (OurAdam's _single_tensor_adam2 branch).
 
 Arithmetic follows _single_tensor_adam (scene/OurAdam.py:249-337): step counters are host

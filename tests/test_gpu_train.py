@@ -1,4 +1,4 @@
-"""GPU parity of the train-step kernels (csrc/train.hip) through their C ABI (include/gsr_train.h)
+"""GPU parity of the train-step kernels (csrc/loss.hip, optim.hip) through their C ABI (include/gsr_train.h)
 against the reference-generated fixtures and the CPU oracle (oracle/train_ref.py), and the
 train-step harness end to end.
 

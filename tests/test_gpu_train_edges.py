@@ -1,4 +1,4 @@
-"""The image side of a training iteration (csrc/train.hip: exposure affine, alpha mask, L1 + SSIM,
+"""The image side of a training iteration (csrc/loss.hip: exposure affine, alpha mask, L1 + SSIM,
 masked inverse-depth L1, depth-only loss) against fp64 torch at the sizes and values where such
 kernels go wrong: one pixel, one pixel past a block, past the exposure grid's cap (a second and a
 third grid-stride trip), images smaller than the 11-tap SSIM window, widths and heights that are no

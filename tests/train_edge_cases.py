@@ -1,6 +1,6 @@
 """Seeded inputs and fp64 torch references for the image side of a training iteration at ragged
 sizes and exact ties: the exposure affine, L1 + SSIM, the masked inverse-depth L1, the depth-only
-loss and their composition (csrc/train.hip).  tests/test_gpu_train_edges.py runs the kernels on
+loss and their composition (csrc/loss.hip).  tests/test_gpu_train_edges.py runs the kernels on
 these; tests/test_train_cpu.py checks that the inputs are well conditioned.  Importable without a GPU.
 
 Every builder returns CPU float32 tensors; every reference evaluates those same float32 numbers in
