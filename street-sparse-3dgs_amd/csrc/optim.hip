@@ -510,6 +510,21 @@ __global__ __launch_bounds__(256) void adam_rowlist_kernel(AdamArgs a, AdamLaneM
 enum AdamKernel { kAdamAuto = 0, kAdamRowBlocks = 1, kAdamElementwise = 2 };
 std::atomic<int> g_adam_kernel{kAdamAuto};
 
+// add_densification_stats for one visible row (radius r > 0; scene/gaussian_model.py:780-793 and
+// train_single.py's max_radii2D update).  accum follows torch.max(norm, accum), which propagates a
+// NaN from either side -- a row whose 2-D gradient went NaN keeps a NaN accumulator until
+// densify_and_prune zeroes it, so it is neither cloned nor split at the next event; fmaxf would
+// return the other operand.  n > a is false for a NaN a, which then stays.
+__device__ inline void densify_stats_row(int64_t i, int r, const float *__restrict__ g2d, float *__restrict__ maxr,
+                                         float *__restrict__ accum, float *__restrict__ denom) {
+    const float gx = g2d[3 * i], gy = g2d[3 * i + 1];
+    const float n = sqrtf(gx * gx + gy * gy);
+    const float a = accum[i];
+    maxr[i] = fmaxf(maxr[i], (float)r);
+    accum[i] = (n > a || n != n) ? n : a;
+    denom[i] = denom[i] + 1.f;
+}
+
 __global__ __launch_bounds__(256) void densify_stats_kernel(int64_t P, const int *__restrict__ radii,
                                                             const float *__restrict__ g2d, float *__restrict__ maxr,
                                                             float *__restrict__ accum, float *__restrict__ denom) {
@@ -517,11 +532,7 @@ __global__ __launch_bounds__(256) void densify_stats_kernel(int64_t P, const int
     if (i >= P) return;
     const int r = radii[i];
     if (r <= 0) return;
-    const float gx = g2d[3 * i], gy = g2d[3 * i + 1];
-    const float n = sqrtf(gx * gx + gy * gy);
-    maxr[i] = fmaxf(maxr[i], (float)r);
-    accum[i] = fmaxf(n, accum[i]);
-    denom[i] = denom[i] + 1.f;
+    densify_stats_row(i, r, g2d, maxr, accum, denom);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -565,7 +576,7 @@ __global__ __launch_bounds__(256) void activate_bwd_kernel(int64_t P, const floa
 
 // The native step's form: also the skybox lock (rows below `skybox` get a zero opacity gradient,
 // train_single.py:217-223), the sparse Adam's "any relevant row" flag (zeroed earlier in the step)
-// and the densification statistics of the same row (densify_stats_kernel's arithmetic).
+// and the densification statistics of the same row (densify_stats_row).
 __global__ __launch_bounds__(256) void activate_bwd_step_kernel(
     int64_t P, const float4 *__restrict__ q_raw, const float *__restrict__ g_s, const float4 *__restrict__ g_q,
     const float *__restrict__ g_o, float *__restrict__ d_s, float4 *__restrict__ d_q, float *__restrict__ d_o,
@@ -582,12 +593,8 @@ __global__ __launch_bounds__(256) void activate_bwd_step_kernel(
         // invisible rows never are) have scale / rotation gradients -- the others are never relevant
         bool live = !sparse_rows;
         if (r > 0) {
-            const float gx = g2d[3 * i], gy = g2d[3 * i + 1];
             if (sparse_rows) live = g2d[3 * i + 2] != 0.f;
-            const float nn = sqrtf(gx * gx + gy * gy);
-            maxr[i] = fmaxf(maxr[i], (float)r);
-            accum[i] = fmaxf(nn, accum[i]);
-            denom[i] = denom[i] + 1.f;
+            densify_stats_row(i, r, g2d, maxr, accum, denom);
         }
         if (live) {
 #pragma unroll

@@ -88,7 +88,7 @@ def densify_and_prune(g, optimizer, max_grad: float, min_opacity: float, extent:
     dst = (RowGroup * len(names))()
     new = []
     for k, p in enumerate(params):
-        w = p[0].numel() if P0 else p.numel() // max(p.shape[0], 1)
+        w = p.shape[1:].numel()  # the row's width, also of a parameter with no rows
         st = optimizer.state.get(p)
         np_ = torch.empty((total,) + tuple(p.shape[1:]), device=dev)
         m = v = None

@@ -138,7 +138,7 @@ class GaussianSet:
         return [
             {"params": [self._xyz], "lr": LR["position_lr_init"] * s, "name": "xyz"},
             *([{"params": [self._features], "lr": LR["feature_lr"], "name": "f_dc+f_rest",
-                "column_lrs": [(0, 3, LR["feature_lr"]), (3, self._features[0].numel(), LR["feature_lr"] / 20.0)]}]
+                "column_lrs": [(0, 3, LR["feature_lr"]), (3, self._features.shape[1:].numel(), LR["feature_lr"] / 20.0)]}]
               if self.joined else
               [{"params": [self._features_dc], "lr": LR["feature_lr"], "name": "f_dc"},
                {"params": [self._features_rest], "lr": LR["feature_lr"] / 20.0, "name": "f_rest"}]),

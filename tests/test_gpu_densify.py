@@ -8,14 +8,21 @@
   forms with torch.bmm (library summation order; 1e-6), and their scaling log(exp(s) / 1.6)
   (CPU exp / log / true division in the fixture run; a few ulps);
 * at larger sizes against the torch restatement (oracle/train_torch_ref.densify_and_prune) on the
-  same generator stream."""
+  same generator stream, and at 20 011 rows against tests/densify_ref.py (numpy float64) on the rows
+  that are not within rounding of a threshold.  tests/test_gpu_densify_edges.py has the ties,
+  overlaps and edge sizes."""
 from __future__ import annotations
 
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import densify_edge_cases as EC  # noqa: E402
+import densify_ref as DR  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -23,20 +30,13 @@ DEV = "cuda"
 
 def _state(P, seed):
     from gs_train.harness import GaussianSet
-    rng = np.random.default_rng(seed)
-    q = rng.normal(size=(P, 4)).astype(np.float32)
-    kw = dict(means3D=rng.normal(size=(P, 3)).astype(np.float32) * 5,
-              shs=rng.normal(size=(P, 16, 3)).astype(np.float32),
-              opacities=rng.uniform(0.01, 0.99, (P, 1)).astype(np.float32),
-              scales=np.exp(rng.normal(-4.0, 0.5, (P, 3))).astype(np.float32), rotations=q, device=DEV)
+    arr, rng = EC.state_arrays(P, seed)  # the draws, shared with the CPU test of their undecided share
+    kw = dict(device=DEV, **{k: arr[k] for k in ("means3D", "shs", "opacities", "scales", "rotations")})
     a = GaussianSet(joined_features=True, **kw)
     b = GaussianSet(joined_features=False, **kw)
-    acc = rng.uniform(0, 0.001, (P, 1)).astype(np.float32)
-    acc[::97] = np.nan  # NaN accumulators are zeroed first
-    maxr = rng.uniform(0, 20, P).astype(np.float32)
     for g in (a, b):
-        g.xyz_gradient_accum = torch.tensor(acc, device=DEV)
-        g.max_radii2D = torch.tensor(maxr, device=DEV)
+        g.xyz_gradient_accum = torch.tensor(arr["accum"], device=DEV)
+        g.max_radii2D = torch.tensor(arr["max_radii"], device=DEV)
     return a, b, rng
 
 
@@ -127,8 +127,12 @@ def test_densify_and_prune_matches_reference(P, first_row):
     a, b, rng = _state(P, 3)
     oa, ob = _optimizers(a, b, rng)
     args = dict(max_grad=0.005, min_opacity=0.05, extent=200.0, percent_dense=0.0001, first_row=first_row)
+    before = {k: getattr(a, k).detach().cpu().numpy().copy() for k in ("_features", "_opacity", "_scaling")}
+    before.update(accum=a.xyz_gradient_accum.cpu().numpy().copy(), max_radii=a.max_radii2D.cpu().numpy().copy())
     torch.manual_seed(11)
     c = densify_and_prune(a, oa, **args)
+    if P == 20_011:
+        _decided_rows_match_float64(a, c, before, args)
     torch.manual_seed(11)
     ref(b, ob, **args)
     n = b._xyz.shape[0]
@@ -148,6 +152,40 @@ def test_densify_and_prune_matches_reference(P, first_row):
     assert float(oa.state[a._xyz]["step"]) == 7.0
     for x, y in ((a.xyz_gradient_accum, b.xyz_gradient_accum), (a.denom, b.denom), (a.max_radii2D, b.max_radii2D)):
         assert torch.equal(x, y)
+
+
+def _decided_rows_match_float64(a, c, before, args):
+    """The plan against tests/densify_ref.py (numpy float64) on every row an fp32 evaluation cannot
+    decide either way (densify_ref.undecided: fewer than 0.1 % are left out).  The output rows are
+    traced to their sources through the first SH coefficient pair; per decided source row, whether
+    its old row, its clone and its children are there is exactly the reference's."""
+    P = before["_opacity"].shape[0]
+    pos = (args["max_grad"], args["min_opacity"], args["extent"], args["percent_dense"], args["first_row"])
+    assert pos == EC.STATE_ARGS
+    bad = DR.undecided(before["_opacity"], before["_scaling"], before["accum"], before["max_radii"], *pos)
+    assert bad.size < 0.001 * P, bad.size
+    decided = np.ones(P, bool)
+    decided[bad] = False
+    clone, split, prune = DR.predicates(before["_opacity"], before["_scaling"], before["accum"], before["max_radii"],
+                                        *pos)
+    key = lambda f: np.ascontiguousarray(f.reshape(f.shape[0], -1)[:, :2]).view(np.uint64).reshape(-1)
+    k_in, k_out = key(before["_features"]), key(a._features.detach().cpu().numpy())
+    order = np.argsort(k_in)
+    assert np.unique(k_in).size == P
+    src = order[np.searchsorted(k_in[order], k_out)]
+    assert np.array_equal(k_in[src], k_out)
+    kept, cloned = c["kept"], c["cloned"]
+    n_child = (c["total"] - kept - cloned) // 2
+    parts = (src[:kept], src[kept:kept + cloned], src[kept + cloned:kept + cloned + n_child],
+             src[kept + cloned + n_child:])
+    want = (~split & ~prune, clone & ~prune, split & ~prune, split & ~prune)
+    for rows, w in zip(parts, want):
+        assert (np.diff(rows) > 0).all()  # each part in source order
+        got = np.zeros(P, bool)
+        got[rows] = True
+        assert np.array_equal(got[decided], w[decided])
+        assert int(got[decided].sum()) == int(w[decided].sum()) > 100
+    assert abs(c["split"] - int(split.sum())) <= bad.size
 
 
 def test_densify_then_train_step_runs():
