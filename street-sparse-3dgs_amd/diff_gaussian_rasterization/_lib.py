@@ -186,6 +186,18 @@ LPIPS_SIGNATURES = {
     "gsr_lpips_accumulate": (_i, [_vp, _vp, _i, _vp, _vp]),
 }
 
+# include/gsr_model_init.h (the model from a cloud, the scaffold rows in front of a chunk); typed by load()
+# like SIGNATURES.  New entry points only: the ABI version stays
+MODEL_INIT_SIGNATURES = {
+    "gsr_model_init_scratch_bytes": (ctypes.c_size_t, [_i64, _i64]),
+    "gsr_model_init_cloud": (_i, [_i64, _vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                  ctypes.POINTER(_f), _vp, _vp]),
+    "gsr_scaffold_merge_scratch_bytes": (ctypes.c_size_t, [_i64]),
+    "gsr_scaffold_merge_count": (_i, [_i64, _i64, _vp, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp, _vp, _vp]),
+    "gsr_scaffold_merge_write": (_i, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 ABI_VERSION = 7
 _lib = None
 
@@ -209,7 +221,7 @@ def load(path: str = LIB_PATH):
         raise RasterizerLibraryError(f"failed to load {path}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(GT_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                               + list(HIER_BUILD_SIGNATURES.items()) + list(HIER_MERGE_SIGNATURES.items())
-                              + list(LPIPS_SIGNATURES.items())):
+                              + list(LPIPS_SIGNATURES.items()) + list(MODEL_INIT_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -14,6 +14,9 @@
   lpips.LpipsModel                 its LPIPS column: one VGG16 pass per frame, fused per-region taps (csrc/lpips.hip)
   hier_build.build_hierarchy       a trained chunk's LOD hierarchy (GaussianHierarchyCreator's step; csrc/hier_build.hip)
   hier_merge.merge_hierarchies     the chunks' hierarchies into the scene's (GaussianHierarchyMerger's step; csrc/hier_merge.hip)
+  model_init.create_from_cloud     a point cloud to a model, with or without a scaffold (create_from_pcd; csrc/model_init.hip)
+  coarse.CoarseTrainStep / TrainCoarse  train_coarse.py's iteration and loop: the degree-1 scaffold
+  scaffold.save_scaffold / load_scaffold  the scaffold's point_cloud.ply and pc_info.txt
 """
 from .loss import l1_ssim, photo_loss  # noqa: F401
 from .optim import Adam  # noqa: F401

@@ -23,13 +23,11 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply_xyz(path) -> np.ndarray:
-    """The x, y, z properties of a PLY file's vertex element as an (N, 3) float32 array (what
-    load_gt_point_cloud takes from plyfile).  Reads `format ascii 1.0` and
-    `format binary_little_endian 1.0` with float or double coordinates; the vertex element may carry
-    other scalar properties, and other elements may follow it.  Raises ValueError on anything else
-    (big-endian data, no vertex element, list properties in or before the vertex element, missing
-    or non-floating coordinates, truncated data)."""
+def read_ply_vertex_header(path):
+    """The header of a PLY file up to its vertex element: (body bytes, format, elements, index of the
+    vertex element, its row count, its [(property name, numpy type)]).  Reads `format ascii 1.0` and
+    `format binary_little_endian 1.0`; raises ValueError on anything else (big-endian data, no vertex
+    element, list properties in or before the vertex element)."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.find(b"end_header")
@@ -68,12 +66,15 @@ def read_ply_xyz(path) -> np.ndarray:
         if any(t is None for _, t in e[2]):
             raise ValueError(f"{path}: list property in or before the vertex element")
     _, count, props = elements[vi]
+    return body, fmt, elements, vi, count, props
+
+
+def read_ply_vertex_columns(path, header, names):
+    """The vertex element's properties `names` as a list of (count,) arrays (float64 from an ascii file,
+    the stored type from a binary one); header: read_ply_vertex_header(path).  Raises ValueError on
+    truncated or malformed data."""
+    body, fmt, elements, vi, count, props = header
     pn = [n for n, _ in props]
-    for c in "xyz":
-        if c not in pn:
-            raise ValueError(f"{path}: the vertex element has no property {c!r}")
-        if dict(props)[c] not in ("f4", "f8"):
-            raise ValueError(f"{path}: vertex property {c!r} is not float or double")
     if fmt[0] == "ascii":
         tok = body.split()
         skip = sum(e[1] * len(e[2]) for e in elements[:vi])
@@ -84,14 +85,31 @@ def read_ply_xyz(path) -> np.ndarray:
             rows = np.array(tok[skip:skip + need], dtype=np.float64).reshape(count, len(props))
         except ValueError as e:
             raise ValueError(f"{path}: malformed ascii vertex data") from e
-        xyz = np.stack([rows[:, pn.index(c)] for c in "xyz"], 1)
-    else:
-        off = sum(e[1] * np.dtype([(n, "<" + t) for n, t in e[2]]).itemsize for e in elements[:vi] if e[2])
-        dt = np.dtype([(n, "<" + t) for n, t in props])
-        if len(body) < off + count * dt.itemsize:
-            raise ValueError(f"{path}: truncated vertex data")
-        rows = np.frombuffer(body, dtype=dt, count=count, offset=off)
-        xyz = np.stack([rows[c] for c in "xyz"], 1)
+        return [rows[:, pn.index(c)] for c in names]
+    off = sum(e[1] * np.dtype([(n, "<" + t) for n, t in e[2]]).itemsize for e in elements[:vi] if e[2])
+    dt = np.dtype([(n, "<" + t) for n, t in props])
+    if len(body) < off + count * dt.itemsize:
+        raise ValueError(f"{path}: truncated vertex data")
+    rows = np.frombuffer(body, dtype=dt, count=count, offset=off)
+    return [rows[c] for c in names]
+
+
+def read_ply_xyz(path) -> np.ndarray:
+    """The x, y, z properties of a PLY file's vertex element as an (N, 3) float32 array (what
+    load_gt_point_cloud takes from plyfile).  Reads `format ascii 1.0` and
+    `format binary_little_endian 1.0` with float or double coordinates; the vertex element may carry
+    other scalar properties, and other elements may follow it.  Raises ValueError on anything else
+    (big-endian data, no vertex element, list properties in or before the vertex element, missing
+    or non-floating coordinates, truncated data)."""
+    header = read_ply_vertex_header(path)
+    props = header[5]
+    pn = [n for n, _ in props]
+    for c in "xyz":
+        if c not in pn:
+            raise ValueError(f"{path}: the vertex element has no property {c!r}")
+        if dict(props)[c] not in ("f4", "f8"):
+            raise ValueError(f"{path}: vertex property {c!r} is not float or double")
+    xyz = np.stack(read_ply_vertex_columns(path, header, "xyz"), 1)
     return np.ascontiguousarray(xyz.astype(np.float32))
 
 
