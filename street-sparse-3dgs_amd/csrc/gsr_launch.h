@@ -70,6 +70,9 @@ hipError_t sort_pairs64(void *tmp, size_t tmp_bytes, const uint64_t *kin, uint64
 size_t key_runs_temp_bytes(size_t n);
 hipError_t key_runs(void *tmp, size_t tmp_bytes, const uint64_t *keys, size_t n, uint64_t *run_key,
                     uint32_t *run_start, uint32_t *n_runs, hipStream_t s);
+// Exclusive prefix sum of n 32-bit counts (lidar.hip: the caller keeps the total below 2^32).
+size_t scan_u32_temp_bytes(size_t n);
+hipError_t scan_u32(void *tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s);
 
 // gtcloud.hip: what a query kernel needs of a gsr_gt_index (include/gsr_gtcloud.h)
 struct GtGrid {

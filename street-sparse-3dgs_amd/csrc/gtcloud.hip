@@ -42,6 +42,7 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_gtcloud.h"
+#include "grid_cell.h"  // cell_of: monotone non-decreasing in v (the exactness argument above)
 #include "gsr_launch.h"
 
 struct gsr_gt_index {
@@ -59,17 +60,6 @@ namespace {
 
 constexpr uint64_t kGtMagic = 0x6773725f67746964ull;  // "gsr_gtid"
 constexpr uint32_t kLaneRun = 16;  // longer runs are shared by the wave
-
-__device__ __forceinline__ uint32_t gt_f2ord(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-inline float gt_ord2f(uint32_t u) {
-    const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    float f;
-    std::memcpy(&f, &b, 4);
-    return f;
-}
 
 __global__ void gt_bbox_init_kernel(uint32_t *bb) {
     if (threadIdx.x < 3) {
@@ -99,16 +89,10 @@ __global__ __launch_bounds__(256) void gt_bbox_kernel(int64_t G, const float *__
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            atomicMin(&bb[k], gt_f2ord(mn[k]));
-            atomicMax(&bb[3 + k], gt_f2ord(mx[k]));
+            atomicMin(&bb[k], f2ord(mn[k]));
+            atomicMax(&bb[3 + k], f2ord(mx[k]));
         }
     }
-}
-
-// the cell coordinate along one axis: monotone non-decreasing in v (the exactness argument above)
-__device__ __forceinline__ int cell_of(float v, float o, float inv_h, int n) {
-    const float t = floorf(__fmul_rn(__fsub_rn(v, o), inv_h));
-    return (int)fminf(fmaxf(t, 0.f), (float)(n - 1));
 }
 
 __device__ __forceinline__ uint64_t cell_key_of(int cx, int cy, int cz, const GtGrid &g) {
@@ -295,8 +279,8 @@ gsr_gt_index *gsr_gt_index_create(int64_t G, const float *points, double thr, vo
     GtGrid g{};
     float ext = 0.f;
     for (int k = 0; k < 3; k++) {
-        g.lo[k] = gt_ord2f(hbb[k]);
-        g.hi[k] = gt_ord2f(hbb[3 + k]);
+        g.lo[k] = ord2f(hbb[k]);
+        g.hi[k] = ord2f(hbb[3 + k]);
         if (!std::isfinite(g.lo[k]) || !std::isfinite(g.hi[k]) || !std::isfinite(g.hi[k] - g.lo[k])) {
             for (void *p : held) (void)hipFree(p);
             set_last_error("gsr_gt_index_create: the cloud has a non-finite coordinate or extent");

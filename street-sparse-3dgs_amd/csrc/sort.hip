@@ -1,4 +1,4 @@
-// sort.hip -- rocPRIM pair sort for the kNN initialisation's Morton order (knn.hip).  The
+// sort.hip -- rocPRIM pair sorts, key runs and scans (knn.hip, gtcloud.hip, lidar.hip).  The
 // rasterizer's depth sort is dsort.hip.  Kept in its own translation unit: rocPRIM's templates
 // dominate compile time.
 #include <cstring>
@@ -53,6 +53,19 @@ hipError_t key_runs(void *tmp, size_t tmp_bytes, const uint64_t *keys, size_t n,
                     uint32_t *run_start, uint32_t *n_runs, hipStream_t s) {
     return rocprim::unique_by_key(tmp, tmp_bytes, keys, rocprim::counting_iterator<uint32_t>(0), run_key, run_start,
                                   n_runs, n, rocprim::equal_to<uint64_t>(), s);
+}
+
+// Exclusive prefix sum of n 32-bit counts (lidar.hip's mesh index: count, scan, fill).
+size_t scan_u32_temp_bytes(size_t n) {
+    size_t bytes = 0;
+    rocprim::exclusive_scan(nullptr, bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n > 0 ? n : 1,
+                            rocprim::plus<uint32_t>());
+    return bytes;
+}
+
+hipError_t scan_u32(void *tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    return rocprim::exclusive_scan(tmp, tmp_bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s);
 }
 
 }  // namespace gsr

@@ -198,6 +198,17 @@ MODEL_INIT_SIGNATURES = {
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/gsr_lidar.h (a chunk's LiDAR cloud: crop, mesh filter, voxel mean); typed by load() like SIGNATURES.
+# New entry points only: the ABI version stays
+LIDAR_SIGNATURES = {
+    "gsr_mesh_index_create": (_vp, [_i64, _vp, _i64, _vp, _d, _vp]),
+    "gsr_mesh_index_destroy": (None, [_vp]),
+    "gsr_mesh_index_info": (_i, [_vp, ctypes.POINTER(_i64), _i]),
+    "gsr_mesh_near_mask": (_i, [_i64, _vp, _vp, _d, ctypes.POINTER(_f), _vp, _vp]),
+    "gsr_voxel_mean_scratch_bytes": (ctypes.c_size_t, [_i64]),
+    "gsr_voxel_mean": (_i, [_i64, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, ctypes.POINTER(_i64), _vp]),
+}
+
 ABI_VERSION = 7
 _lib = None
 
@@ -221,7 +232,8 @@ def load(path: str = LIB_PATH):
         raise RasterizerLibraryError(f"failed to load {path}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(GT_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                               + list(HIER_BUILD_SIGNATURES.items()) + list(HIER_MERGE_SIGNATURES.items())
-                              + list(LPIPS_SIGNATURES.items()) + list(MODEL_INIT_SIGNATURES.items())):
+                              + list(LPIPS_SIGNATURES.items()) + list(MODEL_INIT_SIGNATURES.items())
+                              + list(LIDAR_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

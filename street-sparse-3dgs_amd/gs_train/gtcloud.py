@@ -25,9 +25,10 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
 
 def read_ply_vertex_header(path):
     """The header of a PLY file up to its vertex element: (body bytes, format, elements, index of the
-    vertex element, its row count, its [(property name, numpy type)]).  Reads `format ascii 1.0` and
-    `format binary_little_endian 1.0`; raises ValueError on anything else (big-endian data, no vertex
-    element, list properties in or before the vertex element)."""
+    vertex element, its row count, its [(property name, numpy type)]).  An element is [name, count,
+    [(property name, numpy type or None for a list)], {list property name: (count type, item type)}].
+    Reads `format ascii 1.0` and `format binary_little_endian 1.0`; raises ValueError on anything else
+    (big-endian data, no vertex element, list properties in or before the vertex element)."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.find(b"end_header")
@@ -38,7 +39,7 @@ def read_ply_vertex_header(path):
         raise ValueError(f"{path}: truncated PLY header")
     body = data[nl + 1:]
     fmt = None
-    elements = []  # [name, count, [(property name, numpy type or None for a list)]]
+    elements = []  # [name, count, [(property name, numpy type or None for a list)], {list name: types}]
     for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
         w = line.split()
         if not w or w[0] in ("comment", "obj_info"):
@@ -46,10 +47,13 @@ def read_ply_vertex_header(path):
         if w[0] == "format":
             fmt = tuple(w[1:])
         elif w[0] == "element" and len(w) == 3:
-            elements.append([w[1], int(w[2]), []])
+            elements.append([w[1], int(w[2]), [], {}])
         elif w[0] == "property" and elements:
             if w[1] == "list":
-                elements[-1][2].append((w[-1], None))
+                if len(w) != 5 or w[2] not in _PLY_TYPES or w[3] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: unsupported PLY property line {line!r}")
+                elements[-1][2].append((w[4], None))
+                elements[-1][3][w[4]] = (_PLY_TYPES[w[2]], _PLY_TYPES[w[3]])
             elif len(w) == 3 and w[1] in _PLY_TYPES:
                 elements[-1][2].append((w[2], _PLY_TYPES[w[1]]))
             else:
@@ -65,7 +69,7 @@ def read_ply_vertex_header(path):
     for e in elements[:vi + 1]:
         if any(t is None for _, t in e[2]):
             raise ValueError(f"{path}: list property in or before the vertex element")
-    _, count, props = elements[vi]
+    count, props = elements[vi][1:3]
     return body, fmt, elements, vi, count, props
 
 
