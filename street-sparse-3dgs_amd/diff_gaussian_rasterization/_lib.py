@@ -209,6 +209,31 @@ LIDAR_SIGNATURES = {
     "gsr_voxel_mean": (_i, [_i64, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, ctypes.POINTER(_i64), _vp]),
 }
 
+
+# include/gsr_chunker.h (the scene partition: cells, per-camera counts, candidates, observation filter).
+# New entry points only: the ABI version stays
+class ChunkGrid(ctypes.Structure):
+    _fields_ = [("x0", _d), ("y0", _d), ("cs", _d), ("n_w", ctypes.c_int32), ("n_h", ctypes.c_int32)]
+
+
+_gp = ctypes.POINTER(ChunkGrid)
+_i64p = ctypes.POINTER(_i64)
+CHUNKER_SIGNATURES = {
+    "gsr_chunk_classify_points": (_i, [_i64, _vp, _vp, _gp, _vp, _vp, _vp]),
+    "gsr_chunk_classify_centers": (_i, [_i64, _vp, _i64, _vp, _gp, _vp, _vp, _vp]),
+    "gsr_chunk_id_range": (_i, [_i64, _vp, _i64p, _vp]),
+    "gsr_chunk_id_table": (_i, [_i64, _vp, _i64, _vp, _vp]),
+    "gsr_chunk_camera_counts": (_i, [_i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "gsr_chunk_candidates_scratch_bytes": (ctypes.c_size_t, [_i64]),
+    "gsr_chunk_candidates_count": (_i, [_i64, _vp, _vp, _vp, _gp, _i, _vp, _i64p, _vp]),
+    "gsr_chunk_candidates_write": (_i, [_i64, _vp, _vp, _vp, _vp, _gp, _i, _vp, _vp, _vp]),
+    "gsr_chunk_obs_filter_scratch_bytes": (ctypes.c_size_t, [_i64]),
+    "gsr_chunk_obs_filter_count": (_i, [_i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64p, _vp]),
+    "gsr_chunk_obs_filter_write": (_i, [_i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "gsr_chunk_points_by_cell_scratch_bytes": (ctypes.c_size_t, [_i64, _i64]),
+    "gsr_chunk_points_by_cell": (_i, [_i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+}
+
 ABI_VERSION = 7
 _lib = None
 
@@ -233,7 +258,7 @@ def load(path: str = LIB_PATH):
     for name, (res, args) in (list(SIGNATURES.items()) + list(GT_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                               + list(HIER_BUILD_SIGNATURES.items()) + list(HIER_MERGE_SIGNATURES.items())
                               + list(LPIPS_SIGNATURES.items()) + list(MODEL_INIT_SIGNATURES.items())
-                              + list(LIDAR_SIGNATURES.items())):
+                              + list(LIDAR_SIGNATURES.items()) + list(CHUNKER_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
