@@ -9,7 +9,7 @@
 //   node  (int32 x 7): depth, parent (-1 = root), start (first Gaussian), count_leafs,
 //                      count_merged, start_children, count_children
 //   box   (float  x 8): minn.xyz, size | maxx.xyz, (unused) -- minn.w holds the node's world size
-// Projected size of a node seen from viewpoint v: +inf when v is inside the box, else
+// Projected size of a node seen from viewpoint v: FLT_MAX when v is inside the box, else
 // size / |v - closest point of the box|.  A node is in the cut when it is small enough
 // (size < target) and its parent is not (or it is a root): all its Gaussians are rendered; a node
 // that is still too big renders only its leaf Gaussians (its children carry on).  The blend
