@@ -209,6 +209,16 @@ LIDAR_SIGNATURES = {
     "gsr_voxel_mean": (_i, [_i64, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, ctypes.POINTER(_i64), _vp]),
 }
 
+# include/gsr_mesh_depth.h (the mesh ray cast and the 16-bit inverse depth encode).
+# New entry points only: the ABI version stays
+MESH_DEPTH_SIGNATURES = {
+    "gsr_mesh_distance_scratch_bytes": (ctypes.c_size_t, [_i64, _i64]),
+    "gsr_mesh_distance_maps": (_i, [_i64, _vp, _i64, _vp, _i64, _vp, _i, _i, _d, _d, _i, _vp, _vp,
+                                    ctypes.POINTER(_i64), _vp]),
+    "gsr_depth_encode_scratch_bytes": (ctypes.c_size_t, [_i64]),
+    "gsr_depth_encode": (_i, [_i64, _i, _i, _vp, _i, _d, _d, _vp, _vp, ctypes.POINTER(_d), ctypes.POINTER(_d), _vp]),
+}
+
 
 # include/gsr_chunker.h (the scene partition: cells, per-camera counts, candidates, observation filter).
 # New entry points only: the ABI version stays
@@ -258,7 +268,8 @@ def load(path: str = LIB_PATH):
     for name, (res, args) in (list(SIGNATURES.items()) + list(GT_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                               + list(HIER_BUILD_SIGNATURES.items()) + list(HIER_MERGE_SIGNATURES.items())
                               + list(LPIPS_SIGNATURES.items()) + list(MODEL_INIT_SIGNATURES.items())
-                              + list(LIDAR_SIGNATURES.items()) + list(CHUNKER_SIGNATURES.items())):
+                              + list(LIDAR_SIGNATURES.items()) + list(MESH_DEPTH_SIGNATURES.items())
+                              + list(CHUNKER_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
