@@ -14,9 +14,13 @@
 //            lane's rank in an SB's list is the SB's position + its wave's prefix + the popcount
 //            of the lower lanes of its wave's word.  Both kernels walk a footprint by row and
 //            column (SBWalk): no division per cell.
-//   level 2  SB -> tiles (tile_bin): one workgroup per SB counts its tiles' instances, writes the
-//            tile ranges, and re-walks the SB list with the same lane-mask ranking per tile to
-//            place every instance at its stable position.
+//   level 2  SB -> tiles (tile_bin): one workgroup per SB; every wave reads its share of the SB list
+//            once, into LDS, and walks it twice: per batch of 64 entries, a ballot per tile row and
+//            per tile column of "the footprint reaches it", a tile's lanes the AND of its row's and
+//            column's ballots.  The first walk counts the tiles' instances (then the tile ranges),
+//            the second places every instance at its stable position: the tile's running base plus
+//            the lanes below in the tile's mask.  tb_split (long lists, in slices) and the local
+//            sort's sb_sort_bin rank the same way (tb_rank).
 //
 // The result is the upstream order inside every tile -- (depth bits, Gaussian id) -- with tiles
 // laid out SB-major instead of row-major; every consumer goes through `ranges`, so the layout of
@@ -517,12 +521,18 @@ __global__ __launch_bounds__(kScatterRows) void sb_scatter_kernel(int P, SBGrid 
 }
 
 // Level 2: one workgroup per SB; wave w owns a contiguous 1/kTBWaves of the SB's list (entries
-// carry the footprint clipped to the SB, so the list is read sequentially).  For each batch of 64
-// entries and each of the SB's tiles (16 at a time), a ballot of "footprint contains the tile"
-// gives the tile's count (pass A) or, after the tile scan, the stable rank of every covering
-// entry (pass B).  Counters and positions are wave-uniform registers: no LDS in the loops.
+// carry the footprint clipped to the SB, so the list is read sequentially).  The wave stages its
+// segment in its own LDS slot with one burst of loads (kTBStage entries per workgroup; a longer
+// segment goes through the slot in chunks) and walks the slot twice: per batch of 64 entries the
+// rows and columns of a tile group become ballots ("footprint reaches row y" / "... column x"), a
+// tile's lanes are the AND of its row's and its column's ballot, and their popcount is the tile's
+// count (pass A) or, after the tile scan, the lane's rank past the tile's running position (pass B).
+// Masks, counters and store bases are wave-uniform (scalar registers).
 #ifndef GSR_TB_WAVES
-#define GSR_TB_WAVES 8  // waves per superblock for short lists (1M Gaussians: 8 > 16 > 4)
+// waves per superblock for short lists (1M Gaussians, DESIGN.md 25.3: 16 waves are no faster -- the
+// walks are bound by scalar issue, not by a wave's length -- and two 16-wave workgroups per CU leave
+// 96 scalar registers per wave, which the tile bases overflow)
+#define GSR_TB_WAVES 8
 #endif
 #ifndef GSR_TB_WAVES_LONG
 #define GSR_TB_WAVES_LONG 16  // ... and for long ones (more than GSR_TB_LONG Gaussians per SB on average)
@@ -533,78 +543,142 @@ __global__ __launch_bounds__(kScatterRows) void sb_scatter_kernel(int P, SBGrid 
 constexpr int kTileGroup = 16;
 constexpr int kTBSplitBlocks = 256;  // tb_split_kernel's grid (items dealt round-robin)
 
-#ifndef GSR_TB_DEPTH
-#define GSR_TB_DEPTH 2  // list batches in flight per wave (loads issued one group ahead)
-#endif
-constexpr int kTBDepth = GSR_TB_DEPTH;
+// List entries a workgroup stages in LDS, C: 6 bytes each (the id and the footprint in 4-bit fields),
+// 42 KiB; with tc[][], 50 KiB at 8 waves (three workgroups per CU, as the registers allow) and 58 KiB
+// at 16 (two).  A wave's slot is kTBStage / kTBWaves entries: 14 batches at 8 waves, 7 at 16.  A
+// 1080p frame of 1M Gaussians has lists of up to ~6100 entries.
+constexpr int kTBStage = 7168;
 
-// Footprint of SB-clipped rect r over tile group [tg, tg + 16) (SB-local row-major), one bit per
-// tile: the column range as a bit run, replicated over the group's rows inside the row range.
-__device__ __forceinline__ uint32_t group_mask(uint32_t r, int tg, int shift) {
-    const int side = 1 << shift;
-    const int x0 = (int)(r & 0xFFu), y0 = (int)((r >> 8) & 0xFFu), x1 = (int)((r >> 16) & 0xFFu),
-              y1 = (int)(r >> 24);
-    if (x1 < x0) return 0u;  // padding entry (0xFF) or empty
-    const uint32_t cols = ((2u << x1) - 1u) & ~((1u << x0) - 1u);  // x1 <= 15
-    const int row0 = tg >> shift, rows = kTileGroup >> shift;     // side <= 16: rows >= 1
-    uint32_t m = 0;
+struct TBStage {
+    uint32_t id[kTBStage];
+    uint16_t fp4[kTBStage];
+};
+
+// A list entry's SB-clipped footprint as tb_rank tests it: first column and row, and the number of
+// columns and rows (no columns for a padding entry, 0xFF: x1 < x0).
+struct TBFoot {
+    int x0, y0;
+    uint32_t nx, ny;
+};
+
+__device__ __forceinline__ TBFoot tb_foot(int x0, int y0, int x1, int y1) {
+    return TBFoot{x0, y0, (uint32_t)max(x1 - x0 + 1, 0), (uint32_t)max(y1 - y0 + 1, 0)};
+}
+
+// The footprint in 4-bit fields, as the walks hold it in LDS (SB-local coordinates are below 16;
+// padding keeps x1 < x0), from the SB list's 8-bit fields and to a TBFoot
+__device__ __forceinline__ uint32_t tb_pack4(uint32_t r) {
+    return (r & 0xFu) | ((r >> 4) & 0xF0u) | ((r >> 8) & 0xF00u) | ((r >> 12) & 0xF000u);
+}
+
+__device__ __forceinline__ TBFoot tb_foot4(uint32_t h) {
+    return tb_foot((int)(h & 0xFu), (int)((h >> 4) & 0xFu), (int)((h >> 8) & 0xFu), (int)((h >> 12) & 0xFu));
+}
+
+// One batch (a lane's entry: Gaussian id, footprint f) against tile group [tg, tg + 16) of an SB of
+// 2^kShift x 2^kShift tiles (SB-local row-major: the group is 16 >> kShift rows of min(side, 16)
+// columns, its first row tg >> kShift).  acc[k]: the wave's instances of tile tg + k so far; place
+// stores a tile's at pt[k] (the wave's first position in the tile, wave-uniform: the store's scalar
+// base) + acc[k] + the lanes below in the tile's mask -- a 32-bit byte offset, which a wave's
+// instances of one tile cannot overflow (a list is below 2^32 entries, a wave's segment 2^29).
+template <int kShift, bool kPlace>
+__device__ __forceinline__ void tb_rank(uint32_t id, const TBFoot &f, int tg, uint32_t (&acc)[kTileGroup],
+                                        uint32_t *const (&pt)[kTileGroup]) {
+    constexpr int kCols = 1 << kShift, kRows = kTileGroup >> kShift;
+    static_assert(kCols <= kTileGroup && kRows * kCols == kTileGroup, "a tile group is whole rows");
+    const int x0 = f.x0, y0 = f.y0;
+    const uint32_t nx = f.nx, ny = f.ny;
+    const int row0 = tg >> kShift;
+    // a ballot straight off a compare is the compare's own lane mask (one v_cmp, no select)
+    bool col[kCols], row[kRows];
+    uint64_t colm[kCols], rowm[kRows];
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int ry = row0 + q;
-        if (q < rows && ry >= y0 && ry <= y1) m |= cols << (q * side);
+    for (int c = 0; c < kCols; c++) {
+        col[c] = (uint32_t)(c - x0) < nx;
+        colm[c] = __builtin_amdgcn_ballot_w64(col[c]);
     }
-    return m;
+#pragma unroll
+    for (int q = 0; q < kRows; q++) {
+        row[q] = (uint32_t)(row0 + q - y0) < ny;
+        rowm[q] = __builtin_amdgcn_ballot_w64(row[q]);
+    }
+#pragma unroll
+    for (int k = 0; k < kTileGroup; k++) {
+        const uint64_t bm = rowm[k >> kShift] & colm[k & (kCols - 1)];  // the tile's lanes: a scalar AND
+        if (kPlace && row[k >> kShift] && col[k & (kCols - 1)])
+            *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(pt[k]) + ((acc[k] + lanes_below(bm)) << 2)) = id;
+        acc[k] += (uint32_t)__popcll(bm);
+    }
 }
 
 // tile_bin's two list walks over entries [a, b) of an SB list at L0, split over the workgroup's
 // kTBWaves waves (wave w: a contiguous 1/kTBWaves): count = per-wave tile counts into tc[w][t];
-// place = stable placement from per-wave tile starts tc[w][t].
+// place = stable placement from per-wave tile starts tc[w][t].  `stage`: the workgroup's LDS slots.
+// `staged` (place): the caller's count walk over the same [a, b) came just before and nothing has
+// written `stage` since, so a segment that fits its slot is still there; a longer one is staged
+// again chunk by chunk (tc[w][] carries the tiles' counts / positions from chunk to chunk).
+template <int kTBWaves, bool kPlace, int kShift>
+__device__ __forceinline__ void tb_walk_s(uint32_t L0, uint32_t a, uint32_t b, const uint2 *__restrict__ sblist,
+                                          uint32_t *__restrict__ point_list, uint32_t (*tc)[kMaxTilesPerSB],
+                                          TBStage &stage, bool staged) {
+    constexpr int kSlot = kTBStage / kTBWaves, kSlotBatches = kSlot / 64;
+    static_assert(kTBStage % (64 * kTBWaves) == 0, "whole batches per wave slot");
+    constexpr int tps = 1 << (2 * kShift);
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const uint32_t n = b - a;
+    const uint32_t seg0 = a + (uint32_t)(((uint64_t)n * w) / kTBWaves), seg1 = a + (uint32_t)(((uint64_t)n * (w + 1)) / kTBWaves);
+    const bool fits = seg1 - seg0 <= (uint32_t)kSlot;
+    uint32_t *slot_id = stage.id + w * kSlot;
+    uint16_t *slot_fp = stage.fp4 + w * kSlot;
+    uint32_t *tcw = tc[w];
+    if (!kPlace && seg0 == seg1)
+        for (int t = lane; t < tps; t += 64) tcw[t] = 0u;
+    for (uint32_t c0 = seg0; c0 < seg1; c0 += (uint32_t)kSlot) {
+        const uint32_t c1 = min(seg1, c0 + (uint32_t)kSlot);
+        const int nb = (int)((c1 - c0 + 63u) >> 6);
+        if (!(kPlace && staged && fits)) {
+            // the chunk's batches: every load issued before the first is waited for
+            uint2 e[kSlotBatches];
+#pragma unroll
+            for (int d = 0; d < kSlotBatches; d++) {
+                const uint32_t i = c0 + (uint32_t)(d * 64 + lane);
+                e[d] = i < c1 ? sblist[L0 + i] : make_uint2(0u, 0xFFu);
+            }
+#pragma unroll
+            for (int d = 0; d < kSlotBatches; d++)
+                if (d < nb) {
+                    slot_id[d * 64 + lane] = e[d].x;
+                    slot_fp[d * 64 + lane] = (uint16_t)tb_pack4(e[d].y);
+                }
+        }
+        const bool first = c0 == seg0;
+#pragma unroll 1
+        for (int tg = 0; tg < tps; tg += kTileGroup) {
+            uint32_t acc[kTileGroup], at[kTileGroup];
+            uint32_t *pt[kTileGroup];
+#pragma unroll
+            for (int k = 0; k < kTileGroup; k++) {
+                const uint32_t v = (kPlace || !first) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)tcw[tg + k]) : 0u;
+                acc[k] = kPlace ? 0u : v;
+                at[k] = kPlace ? v : 0u;
+                pt[k] = point_list + at[k];
+            }
+            for (int d = 0; d < nb; d++)
+                tb_rank<kShift, kPlace>(slot_id[d * 64 + lane], tb_foot4(slot_fp[d * 64 + lane]), tg, acc, pt);
+            if ((!kPlace || !fits) && lane == 0)
+#pragma unroll
+                for (int k = 0; k < kTileGroup; k++) tcw[tg + k] = at[k] + acc[k];
+        }
+    }
+}
+
 template <int kTBWaves, bool kPlace>
 __device__ __forceinline__ void tb_walk(const SBGrid &sg, uint32_t L0, uint32_t a, uint32_t b,
                                         const uint2 *__restrict__ sblist, uint32_t *__restrict__ point_list,
-                                        uint32_t (*tc)[kMaxTilesPerSB]) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tps = 1 << (2 * sg.shift);
-    const uint32_t n = b - a;
-    const uint32_t seg0 = a + (uint32_t)(((uint64_t)n * w) / kTBWaves), seg1 = a + (uint32_t)(((uint64_t)n * (w + 1)) / kTBWaves);
-    const uint64_t lt = (1ull << lane) - 1ull;
-    // the wave's list segment in groups of kTBDepth batches: group n + 1's entries are loaded
-    // while group n is ranked (one dependent load latency per group instead of one per batch)
-    const auto load = [&](uint32_t gb, uint2 *e) {
-#pragma unroll
-        for (int d = 0; d < kTBDepth; d++) {
-            const uint32_t i = gb + (uint32_t)(d * 64 + lane);
-            e[d] = i < seg1 ? sblist[L0 + i] : make_uint2(0u, 0xFFu);
-        }
-    };
-    constexpr uint32_t kGroup = 64 * kTBDepth;
-    for (int tg = 0; tg < tps; tg += kTileGroup) {
-        uint32_t acc[kTileGroup];
-#pragma unroll
-        for (int k = 0; k < kTileGroup; k++) acc[k] = kPlace ? (tg + k < tps ? tc[w][tg + k] : 0u) : 0u;
-        uint2 cur[kTBDepth], nxt[kTBDepth];
-        load(seg0, cur);
-        for (uint32_t gb = seg0; gb < seg1; gb += kGroup) {
-            load(gb + kGroup, nxt);
-#pragma unroll
-            for (int d = 0; d < kTBDepth; d++) {
-                const uint32_t m = group_mask(cur[d].y, tg, sg.shift);
-#pragma unroll
-                for (int k = 0; k < kTileGroup; k++) {
-                    const bool hit = (m >> k) & 1u;
-                    const uint64_t bm = __ballot(hit);
-                    if (kPlace && hit) point_list[acc[k] + (uint32_t)__popcll(bm & lt)] = cur[d].x;
-                    acc[k] += (uint32_t)__popcll(bm);
-                }
-            }
-#pragma unroll
-            for (int d = 0; d < kTBDepth; d++) cur[d] = nxt[d];
-        }
-        if (!kPlace && lane == 0)
-#pragma unroll
-            for (int k = 0; k < kTileGroup; k++)
-                if (tg + k < tps) tc[w][tg + k] = acc[k];
-    }
+                                        uint32_t (*tc)[kMaxTilesPerSB], TBStage &stage, bool staged = false) {
+    if (sg.shift == 2) tb_walk_s<kTBWaves, kPlace, 2>(L0, a, b, sblist, point_list, tc, stage, staged);
+    else if (sg.shift == 3) tb_walk_s<kTBWaves, kPlace, 3>(L0, a, b, sblist, point_list, tc, stage, staged);
+    else tb_walk_s<kTBWaves, kPlace, 4>(L0, a, b, sblist, point_list, tc, stage, staged);
 }
 
 // Per-wave tile counts tc[w][t] -> per-wave starts, tiles in SB-local row-major order from `base`
@@ -663,13 +737,14 @@ __global__ __launch_bounds__(64 * kTBWaves) void tile_bin_kernel(SBGrid sg, int 
     const int s = blockIdx.x;
     if (tb_flag && tb_flag[s]) return;  // a long list: binned in slices (tb_split_kernel)
     __shared__ uint32_t tc[kTBWaves][kMaxTilesPerSB];
+    __shared__ TBStage stage;
     const uint32_t L0 = base_g[s], L = base_g[s + 1] - L0;
-    tb_walk<kTBWaves, false>(sg, L0, 0u, L, sblist, point_list, tc);  // pass A: per-wave tile counts
+    tb_walk<kTBWaves, false>(sg, L0, 0u, L, sblist, point_list, tc, stage);  // pass A: per-wave tile counts
     __syncthreads();
     // tile bases (SB-local row-major tile order, waves in list order) and the tile ranges
     tb_bases<kTBWaves>(sg, gx, gy, s, base_i[s], tc, nullptr, nullptr, ranges);
     __syncthreads();
-    tb_walk<kTBWaves, true>(sg, L0, 0u, L, sblist, point_list, tc);  // pass B: stable placement
+    tb_walk<kTBWaves, true>(sg, L0, 0u, L, sblist, point_list, tc, stage, true);  // pass B: stable placement
 }
 
 // Long SB lists (tile_bin split): the SB's list in nsl slices of ~L / nsl entries, one work item
@@ -692,6 +767,7 @@ __global__ __launch_bounds__(64 * kTBWaves) void tb_split_kernel(SBGrid sg, int 
     if (*kdev > cap) return;
     __shared__ uint32_t tc[kTBWaves][kMaxTilesPerSB];
     __shared__ uint32_t s_tot[kMaxTilesPerSB], s_pre[kMaxTilesPerSB];
+    __shared__ TBStage stage;
     const int tps = 1 << (2 * sg.shift);
     const uint32_t n = tb_flag[sg.nsb];
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
@@ -702,7 +778,7 @@ __global__ __launch_bounds__(64 * kTBWaves) void tb_split_kernel(SBGrid sg, int 
         const uint32_t L0 = base_g[s], L = base_g[s + 1] - L0;
         const uint32_t Ls = (L + nsl - 1u) / nsl;
         const uint32_t a = min(L, j * Ls), b = min(L, a + Ls);
-        tb_walk<kTBWaves, false>(sg, L0, a, b, sblist, point_list, tc);
+        tb_walk<kTBWaves, false>(sg, L0, a, b, sblist, point_list, tc, stage);
         __syncthreads();
         if (!kPlace) {
             for (int t = threadIdx.x; t < tps; t += 64 * kTBWaves) {
@@ -725,7 +801,7 @@ __global__ __launch_bounds__(64 * kTBWaves) void tb_split_kernel(SBGrid sg, int 
             __syncthreads();
             tb_bases<kTBWaves>(sg, gx, gy, s, base_i[s], tc, s_tot, s_pre, j == 0 ? ranges : nullptr);
             __syncthreads();
-            tb_walk<kTBWaves, true>(sg, L0, a, b, sblist, point_list, tc);
+            tb_walk<kTBWaves, true>(sg, L0, a, b, sblist, point_list, tc, stage, true);
         }
         __syncthreads();  // tc / s_tot reused by the next item
     }
@@ -744,7 +820,7 @@ __global__ __launch_bounds__(64 * kTBWaves) void tb_split_kernel(SBGrid sg, int 
 //    digit scan, the reorder through LDS (keys and 16-bit list positions ping-pong).  Stability
 //    keeps id order among equal depths: the (depth bits, id) order of upstream's keys.
 // 3. The sorted (id, footprint) pairs, gathered once from the SB list into LDS, then tile_bin's
-//    two ballot passes (per-wave tile counts, tile bases and ranges, stable placement) over them.
+//    two walks (per-wave tile counts, tile bases and ranges, stable placement: tb_rank) over them.
 // ---------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ uint64_t lanes_with_digit(uint32_t d, uint64_t valid) {
@@ -756,6 +832,39 @@ __device__ __forceinline__ uint64_t lanes_with_digit(uint32_t d, uint64_t valid)
         m &= bit ? bb : ~bb;
     }
     return m;
+}
+
+// sb_sort_bin's tile binning: tb_rank over a wave's kmax batches of sorted entries, held in LDS as
+// ids[] and 4-bit-field footprints fp4[] (count: the wave's tile counts into tcw[t]; place: stable
+// placement from its tile starts tcw[t]).  A lane reads the entries it wrote itself.
+template <bool kPlace, int kShift>
+__device__ __forceinline__ void sbs_walk_s(const uint32_t *ids, const uint16_t *fp4, int kmax, uint32_t *tcw,
+                                           uint32_t *__restrict__ point_list) {
+    constexpr int tps = 1 << (2 * kShift);
+    const int lane = threadIdx.x & 63;
+#pragma unroll 1
+    for (int tg = 0; tg < tps; tg += kTileGroup) {
+        uint32_t acc[kTileGroup];
+        uint32_t *pt[kTileGroup];
+#pragma unroll
+        for (int k = 0; k < kTileGroup; k++) {
+            acc[k] = 0u;
+            pt[k] = point_list + (kPlace ? (uint32_t)__builtin_amdgcn_readfirstlane((int)tcw[tg + k]) : 0u);
+        }
+        for (int b = 0; b < kmax; b++)
+            tb_rank<kShift, kPlace>(ids[b * 64 + lane], tb_foot4(fp4[b * 64 + lane]), tg, acc, pt);
+        if (!kPlace && lane == 0)
+#pragma unroll
+            for (int k = 0; k < kTileGroup; k++) tcw[tg + k] = acc[k];
+    }
+}
+
+template <bool kPlace>
+__device__ __forceinline__ void sbs_walk(int shift, const uint32_t *ids, const uint16_t *fp4, int kmax, uint32_t *tcw,
+                                         uint32_t *__restrict__ point_list) {
+    if (shift == 2) sbs_walk_s<kPlace, 2>(ids, fp4, kmax, tcw, point_list);
+    else if (shift == 3) sbs_walk_s<kPlace, 3>(ids, fp4, kmax, tcw, point_list);
+    else sbs_walk_s<kPlace, 4>(ids, fp4, kmax, tcw, point_list);
 }
 
 // __launch_bounds__(1024, 8): registers budgeted for 8 waves per SIMD -- two 1024-thread
@@ -784,7 +893,6 @@ __global__ __launch_bounds__(kSBThreads, 8) void sb_sort_bin_kernel(SBGrid sg, i
     const int side = 1 << sg.shift, tps = side * side;
     const int ox = (s % sg.nsbx) * side, oy = (s / sg.nsbx) * side;
     const uint32_t L0 = base_g[s], n = base_g[s + 1] - L0;
-    const uint64_t lt = (1ull << lane) - 1ull;
     const int wb = w * kSBItems * 64;  // the wave's first list position
     SB_STAMP(0);
     if (GSR_SB_TRACE && t == 0) g_sb_trace[min(blockIdx.x, 2047u) * 8 + 7] = n;
@@ -898,42 +1006,32 @@ __global__ __launch_bounds__(kSBThreads, 8) void sb_sort_bin_kernel(SBGrid sg, i
     }
 
     SB_STAMP(2);
-    // 3. the sorted (id, footprint) pairs into registers: sorted position e = wb + 64 k + lane is
-    // held by that lane as item k (pos[] after the last pass), so the wave's tile binning below runs
-    // over its own 512 consecutive sorted positions with no LDS and no further gathers
-    uint32_t gid[kSBItems], gfp[kSBItems];
+    // 3. the sorted (id, footprint) pairs into LDS (the sort's buffers are free: ids over the keys,
+    // footprints in 4-bit fields over the positions): sorted position e = wb + 64 k + lane is held
+    // by that lane as item k (pos[] after the last pass) and written and read back by that lane
+    // alone, so the wave's tile binning below runs over its own 512 consecutive sorted positions
+    // with no barrier and no further gathers
+    {
+        uint2 v[kSBItems];
 #pragma unroll
-    for (int k = 0; k < kSBItems; k++) {
-        const uint32_t e = (uint32_t)(wb + k * 64 + lane);
-        gid[k] = 0u;
-        gfp[k] = 0xFFu;  // padding: an empty footprint (x1 < x0)
-        if (e < n) {
-            const uint2 v = reinterpret_cast<const uint2 *>(sblist + L0 + min((uint32_t)pos[k], n - 1u))[0];
-            gid[k] = v.x;  // (pos: a permutation of [0, n))
-            gfp[k] = v.y;
+        for (int k = 0; k < kSBItems; k++) {
+            const uint32_t e = (uint32_t)(wb + k * 64 + lane);
+            v[k] = make_uint2(0u, 0xFFu);  // padding: an empty footprint (x1 < x0)
+            if (e < n)  // (pos: a permutation of [0, n))
+                v[k] = reinterpret_cast<const uint2 *>(sblist + L0 + min((uint32_t)pos[k], n - 1u))[0];
+        }
+#pragma unroll
+        for (int k = 0; k < kSBItems; k++) {
+            s_key[wb + k * 64 + lane] = v[k].x;
+            s_pos[wb + k * 64 + lane] = (uint16_t)tb_pack4(v[k].y);
         }
     }
     SB_STAMP(3);
-    // tile binning over the sorted list (tile_bin's two ballot passes): wave w owns sorted
+    // tile binning over the sorted list (tile_bin's two walks): wave w owns sorted
     // positions [wb, wb + 512), batch k = its item k
     uint32_t(*tc)[256] = s_wh;
     const int kmax = wb >= (int)n ? 0 : min(kSBItems, ((int)n - wb + 63) / 64);  // the wave's non-empty items
-    for (int tg = 0; tg < tps; tg += kTileGroup) {
-        uint32_t cnt[kTileGroup];
-#pragma unroll
-        for (int k = 0; k < kTileGroup; k++) cnt[k] = 0u;
-#pragma unroll
-        for (int b = 0; b < kSBItems; b++) {
-            if (b >= kmax) break;
-            const uint32_t m = group_mask(gfp[b], tg, sg.shift);
-#pragma unroll
-            for (int k = 0; k < kTileGroup; k++) cnt[k] += (uint32_t)__popcll(__ballot((m >> k) & 1u));
-        }
-        if (lane == 0)
-#pragma unroll
-            for (int k = 0; k < kTileGroup; k++)
-                if (tg + k < tps) tc[w][tg + k] = cnt[k];
-    }
+    sbs_walk<false>(sg.shift, s_key + wb, s_pos + wb, kmax, tc[w], point_list);
     __syncthreads();
     if (w == 0) {
         uint32_t carry = 0;
@@ -963,23 +1061,7 @@ __global__ __launch_bounds__(kSBThreads, 8) void sb_sort_bin_kernel(SBGrid sg, i
     }
     __syncthreads();
     SB_STAMP(4);
-    for (int tg = 0; tg < tps; tg += kTileGroup) {
-        uint32_t pk[kTileGroup];
-#pragma unroll
-        for (int k = 0; k < kTileGroup; k++) pk[k] = tg + k < tps ? tc[w][tg + k] : 0u;
-#pragma unroll
-        for (int b = 0; b < kSBItems; b++) {
-            if (b >= kmax) break;
-            const uint32_t m = group_mask(gfp[b], tg, sg.shift);
-#pragma unroll
-            for (int k = 0; k < kTileGroup; k++) {
-                const bool hit = (m >> k) & 1u;
-                const uint64_t bm = __ballot(hit);
-                if (hit) point_list[pk[k] + (uint32_t)__popcll(bm & lt)] = gid[b];
-                pk[k] += (uint32_t)__popcll(bm);
-            }
-        }
-    }
+    sbs_walk<true>(sg.shift, s_key + wb, s_pos + wb, kmax, tc[w], point_list);
     __syncthreads();
     SB_STAMP(5);
 }
