@@ -244,6 +244,19 @@ CHUNKER_SIGNATURES = {
     "gsr_chunk_points_by_cell": (_i, [_i64, _vp, _i64, _vp, _vp, _vp, _vp]),
 }
 
+# include/gsr_views.h (training views: the Lanczos resize plan and the compact view's expansion).
+# New entry points only: the ABI version stays
+_i32p = ctypes.POINTER(ctypes.c_int32)
+VIEWS_SIGNATURES = {
+    "gsr_resize_plan_create": (_vp, [_i, _i, _i, _i]),
+    "gsr_resize_plan_destroy": (None, [_vp]),
+    "gsr_resize_plan_info": (_i, [_vp, _i64p, _i]),
+    "gsr_resize_plan_tables": (_i, [_vp, _i, _i32p, _i32p]),
+    "gsr_resize_scratch_bytes": (ctypes.c_size_t, [_vp, _i]),
+    "gsr_resize_lanczos_u8": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "gsr_view_expand": (_i, [_i, _i, _vp, _vp, _i, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+}
+
 ABI_VERSION = 7
 _lib = None
 
@@ -269,7 +282,7 @@ def load(path: str = LIB_PATH):
                               + list(HIER_BUILD_SIGNATURES.items()) + list(HIER_MERGE_SIGNATURES.items())
                               + list(LPIPS_SIGNATURES.items()) + list(MODEL_INIT_SIGNATURES.items())
                               + list(LIDAR_SIGNATURES.items()) + list(MESH_DEPTH_SIGNATURES.items())
-                              + list(CHUNKER_SIGNATURES.items())):
+                              + list(CHUNKER_SIGNATURES.items()) + list(VIEWS_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
