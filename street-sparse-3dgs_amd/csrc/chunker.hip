@@ -238,21 +238,16 @@ struct CandLayout {
 
 CandLayout cand_layout(char *base, int64_t n) {
     CandLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off = align_up(off + bytes, 256);
-        return p;
-    };
+    Carve c(base);
     const size_t nw = (size_t)((std::max<int64_t>(n, 1) + 63) / 64) + 1;
-    L.cnt = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * nw));
-    L.pre = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * nw));
+    L.cnt = c.take<uint32_t>(sizeof(uint32_t) * nw);
+    L.pre = c.take<uint32_t>(sizeof(uint32_t) * nw);
     size_t bytes = 0;
     (void)rocprim::exclusive_scan(nullptr, bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, nw,
                                   rocprim::plus<uint32_t>());
     L.tmp_bytes = bytes;
-    L.tmp = take(bytes);
-    L.total = off;
+    L.tmp = c.take(bytes);
+    L.total = c.off;
     return L;
 }
 
@@ -323,20 +318,15 @@ struct ObsLayout {
 
 ObsLayout obs_layout(char *base, int64_t P) {
     ObsLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off = align_up(off + bytes, 256);
-        return p;
-    };
+    Carve c(base);
     const size_t n = (size_t)std::max<int64_t>(P, 0) + 1;
-    L.counts = reinterpret_cast<int64_t *>(take(sizeof(int64_t) * n));
+    L.counts = c.take<int64_t>(sizeof(int64_t) * n);
     size_t bytes = 0;
     (void)rocprim::exclusive_scan(nullptr, bytes, (const int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, n,
                                   rocprim::plus<int64_t>());
     L.tmp_bytes = bytes;
-    L.tmp = take(bytes);
-    L.total = off;
+    L.tmp = c.take(bytes);
+    L.total = c.off;
     return L;
 }
 
@@ -379,19 +369,14 @@ int key_bits(int64_t cells) {  // keys 0 .. cells
 
 CellLayout cell_layout(char *base, int64_t N, int64_t cells) {
     CellLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off = align_up(off + bytes, 256);
-        return p;
-    };
+    Carve c(base);
     const size_t n = (size_t)std::max<int64_t>(N, 1);
-    L.kin = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * n));
-    L.kout = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * n));
-    L.vin = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * n));
+    L.kin = c.take<uint32_t>(sizeof(uint32_t) * n);
+    L.kout = c.take<uint32_t>(sizeof(uint32_t) * n);
+    L.vin = c.take<uint32_t>(sizeof(uint32_t) * n);
     L.tmp_bytes = sort_pairs_temp_bytes(n, key_bits(cells));
-    L.tmp = take(L.tmp_bytes);
-    L.total = off;
+    L.tmp = c.take(L.tmp_bytes);
+    L.total = c.off;
     return L;
 }
 

@@ -23,6 +23,7 @@
 #include "../../include/gsr.h"
 #include "../../include/gsr_densify.h"
 #include "../../include/gsr_gtcloud.h"
+#include "grid_cell.h"
 #include "gsr_launch.h"
 
 namespace gsr {
@@ -51,24 +52,19 @@ struct DensifyLayout {
 
 DensifyLayout densify_layout(char *base, int64_t P0) {
     DensifyLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off = align_up(off + bytes, 256);
-        return p;
-    };
+    Carve c(base);
     const size_t n = (size_t)(P0 > 0 ? P0 : 1);
-    L.flags = reinterpret_cast<Cnt4 *>(take(sizeof(Cnt4) * n));
-    L.pre = reinterpret_cast<Cnt4 *>(take(sizeof(Cnt4) * n));
-    L.tot = reinterpret_cast<Cnt4 *>(take(sizeof(Cnt4)));
-    L.map = reinterpret_cast<uint2 *>(take(sizeof(uint2) * 3 * n));  // at most P0 + 2 * P0 rows
+    L.flags = c.take<Cnt4>(sizeof(Cnt4) * n);
+    L.pre = c.take<Cnt4>(sizeof(Cnt4) * n);
+    L.tot = c.take<Cnt4>(sizeof(Cnt4));
+    L.map = c.take<uint2>(sizeof(uint2) * 3 * n);  // at most P0 + 2 * P0 rows
     size_t bytes = 0;
     rocprim::exclusive_scan(nullptr, bytes, (const Cnt4 *)nullptr, (Cnt4 *)nullptr, Cnt4{0, 0, 0, 0}, n, Cnt4Plus());
     L.tmp_bytes = bytes;
-    L.tmp = take(bytes);
-    L.skip = reinterpret_cast<uint8_t *>(take(n));
-    L.far = reinterpret_cast<uint8_t *>(take(n));
-    L.total = off;
+    L.tmp = c.take(bytes);
+    L.skip = c.take<uint8_t>(n);
+    L.far = c.take<uint8_t>(n);
+    L.total = c.off;
     return L;
 }
 

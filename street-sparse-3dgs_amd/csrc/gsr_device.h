@@ -503,6 +503,27 @@ __device__ __forceinline__ float gauss_p2(float adxdx_s, float bdx_s, float c_s,
 
 __host__ __device__ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// A scratch buffer carved into 256-byte slots: every slot starts on 256 bytes (of an aligned base) and
+// the next one follows at the size rounded up to 256.  base may be NULL (a size query: take() gives
+// NULL); off is the bytes taken so far, the buffer's size after the last take.
+struct Carve {
+    char *base;
+    size_t off = 0;
+    __host__ __device__ explicit Carve(void *b) : base(static_cast<char *>(b)) {}
+    template <class T = void>
+    __host__ __device__ T *take(size_t bytes) {
+        char *p = base ? base + off : nullptr;
+        off = align_up(off + bytes, 256);
+        return reinterpret_cast<T *>(p);
+    }
+};
+
+inline int bits_for(uint64_t n) {  // the bits that hold 0 .. n - 1 (0 for n = 1)
+    int b = 0;
+    while (b < 64 && ((n - 1) >> b) != 0) b++;
+    return b;
+}
+
 // One 64-B render record per Gaussian (written by the preprocess): everything a
 // tile instance needs sits in one cache line, so the render kernels gather 1 line per instance.
 struct alignas(16) GRec {

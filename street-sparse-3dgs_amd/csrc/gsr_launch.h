@@ -62,7 +62,7 @@ void launch_mark_visible(int P, const float *means3D, const float *view, uint8_t
 size_t sort_pairs_temp_bytes(size_t n, int end_bit);
 hipError_t sort_pairs(void *tmp, size_t tmp_bytes, const uint32_t *kin, uint32_t *kout, const uint32_t *vin,
                       uint32_t *vout, size_t n, int end_bit, hipStream_t s);
-// Stable sort of n (64-bit key, value) pairs over key bits [0, end_bit) (gtcloud.hip's cell keys).
+// Stable sort of n (64-bit key, value) pairs over key bits [0, end_bit) (grid_cell.h's cell keys).
 size_t sort_pairs64_temp_bytes(size_t n, int end_bit);
 hipError_t sort_pairs64(void *tmp, size_t tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint32_t *vin,
                         uint32_t *vout, size_t n, int end_bit, hipStream_t s);
@@ -74,16 +74,14 @@ hipError_t key_runs(void *tmp, size_t tmp_bytes, const uint64_t *keys, size_t n,
 size_t scan_u32_temp_bytes(size_t n);
 hipError_t scan_u32(void *tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s);
 
-// gtcloud.hip: what a query kernel needs of a gsr_gt_index (include/gsr_gtcloud.h)
-struct GtGrid {
-    const float4 *pts;          // the cloud in cell order (w unused)
-    const uint64_t *cell_key;   // ascending keys of the occupied cells
-    const uint32_t *cell_start; // n_cells + 1: first point of each cell, then G
-    uint32_t n_cells;
-    float lo[3], hi[3];         // the cloud's fp32 bounding box
-    float inv_h;
-    int32_t n[3];               // cells per axis
-};
+// cell_grid.hip: the fp32 bounding box of the N rows of xyz with keep[i] != 0 (keep may be NULL: all),
+// by ordered-integer atomics into eight words (grid_cell.h: kBBoxWords, bbox_words_init, ord2f) that
+// the caller's own init kernel has set; whether a counted coordinate is NaN or Inf, and the rows counted.
+void launch_bbox(int64_t N, const float *xyz, const uint8_t *keep, uint32_t *words, hipStream_t s,
+                 int max_blocks = 1024);
+
+// gtcloud.hip: what a query kernel needs of a gsr_gt_index (grid_cell.h)
+struct GtGrid;
 bool gt_grid_of(const void *index, GtGrid *out);  // false: NULL or not a live index
 // T: the largest fp32 <= thr^2 (thr a double); reach: an fp32 upper bound of the per-axis distance
 // of any point with d2 <= T.  false: thr not finite, <= 0 or thr^2 below the fp32 normal range

@@ -40,6 +40,7 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_hier_build.h"
+#include "grid_cell.h"  // ord2f, the bounding box's words
 #include "gsr_launch.h"
 #include "hier_level.h"
 
@@ -52,49 +53,11 @@ constexpr float kSurfaceP = 1.6075f;
 constexpr float kMinEigen = 1e-14f;
 constexpr int kJacobiSweeps = 8;
 
-__device__ __forceinline__ uint32_t f2ord(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
 // ---- A. order ------------------------------------------------------------------------------
 
 __global__ void hb_init_kernel(uint32_t *bb, uint64_t *ctl) {
-    if (threadIdx.x < 3) {
-        bb[threadIdx.x] = 0xffffffffu;
-        bb[3 + threadIdx.x] = 0u;
-    }
+    bbox_words_init(bb);
     if (threadIdx.x < 8) ctl[threadIdx.x] = 0ull;
-}
-
-__global__ __launch_bounds__(kThreads) void hb_bounds_kernel(int64_t P, const float *__restrict__ xyz, uint32_t *bb) {
-    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float v = xyz[3 * i + k];
-            mn[k] = fminf(mn[k], v);
-            mx[k] = fmaxf(mx[k], v);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) {
-            mn[k] = fminf(mn[k], __shfl_xor(mn[k], o, kWave));
-            mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o, kWave));
-        }
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            atomicMin(&bb[k], f2ord(mn[k]));
-            atomicMax(&bb[3 + k], f2ord(mx[k]));
-        }
-    }
 }
 
 __device__ __forceinline__ uint64_t spread21(uint64_t x) {  // 21 bits -> every third bit
@@ -430,22 +393,21 @@ struct BuildScratch {
 using hlevel::level_tiles;  // a level holds at most P nodes
 
 size_t build_scratch(int64_t P, size_t sort_bytes, BuildScratch *sc, char *base) {
-    size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at = align_up(at + bytes, 256);
-        return base ? base + o : nullptr;
-    };
+    Carve c(base);
     const size_t p = (size_t)P, nt = (size_t)level_tiles(P);
-    char *ctl = take(8 * 8), *bb = take(8 * 4), *key_in = take(8 * p), *key = take(8 * p), *row_in = take(4 * p);
-    char *row = take(4 * p), *kids = take(8 * p), *tsum = take(4 * nt), *toff = take(8 * nt), *tmp = take(sort_bytes);
-    if (sc)
-        *sc = BuildScratch{reinterpret_cast<uint64_t *>(ctl),     reinterpret_cast<uint32_t *>(bb),
-                           reinterpret_cast<uint64_t *>(key_in),  reinterpret_cast<uint64_t *>(key),
-                           reinterpret_cast<uint32_t *>(row_in),  reinterpret_cast<uint32_t *>(row),
-                           reinterpret_cast<int2 *>(kids),        reinterpret_cast<uint32_t *>(tsum),
-                           reinterpret_cast<uint64_t *>(toff),    tmp};
-    return at;
+    BuildScratch b{};
+    b.ctl = c.take<uint64_t>(8 * 8);
+    b.bb = c.take<uint32_t>(kBBoxWords * 4);
+    b.key_in = c.take<uint64_t>(8 * p);
+    b.key = c.take<uint64_t>(8 * p);
+    b.row_in = c.take<uint32_t>(4 * p);
+    b.row = c.take<uint32_t>(4 * p);
+    b.kids = c.take<int2>(8 * p);
+    b.tile_sum = c.take<uint32_t>(4 * nt);
+    b.tile_off = c.take<uint64_t>(8 * nt);
+    b.sort_tmp = c.take(sort_bytes);
+    if (sc) *sc = b;
+    return c.off;
 }
 
 int fail_build(int code, const std::string &m) {
@@ -477,8 +439,7 @@ int hier_build_tree(int64_t P, const float *xyz, int *nodes, int *leaf_rows, std
 
     // A. order
     hipLaunchKernelGGL(hb_init_kernel, dim3(1), dim3(64), 0, s, sc.bb, sc.ctl);
-    const int64_t bounds_blocks = std::min<int64_t>((P + kThreads - 1) / kThreads, 2048);
-    hipLaunchKernelGGL(hb_bounds_kernel, dim3((unsigned)bounds_blocks), dim3(kThreads), 0, s, P, xyz, sc.bb);
+    launch_bbox(P, xyz, nullptr, sc.bb, s, 2048);
     hipLaunchKernelGGL(hb_keys_kernel, blocks(P, kThreads), dim3(kThreads), 0, s, P, xyz, sc.bb, sc.key_in, sc.row_in);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = sort_pairs64(sc.sort_tmp, sort_bytes, sc.key_in, sc.key, sc.row_in, sc.row, (size_t)P, 63, s);

@@ -342,28 +342,27 @@ struct MergeScratch {
 };
 
 size_t merge_scratch(int64_t C, int64_t T, MergeScratch *sc, char *base) {
-    size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at = align_up(at + bytes, 256);
-        return base ? base + o : nullptr;
-    };
+    Carve cv(base);
     const size_t c = (size_t)C, t = (size_t)T, nt = (size_t)hlevel::level_tiles((T + C) / 2 + 1);
-    const size_t bb = gsr_hier_build_scratch_bytes(C);
-    char *ctl = take(64), *first = take(8 * (c + 1)), *kc = take(8 * c), *root = take(4 * c), *active = take(4 * c);
-    char *flag = take(4 * t), *ret = take(t), *ekids = take(8 * t), *kid = take(4 * (t + c)), *tsum = take(4 * nt);
-    char *toff = take(8 * nt), *tnodes = take(28 * (2 * c - 1)), *tleaf = take(4 * (2 * c - 1)), *txyz = take(12 * c);
-    char *build = take(bb);
-    if (sc)
-        *sc = MergeScratch{reinterpret_cast<uint64_t *>(ctl),  reinterpret_cast<int64_t *>(first),
-                           reinterpret_cast<uint64_t *>(kc),   reinterpret_cast<int *>(root),
-                           reinterpret_cast<int *>(active),    reinterpret_cast<uint32_t *>(flag),
-                           reinterpret_cast<uint8_t *>(ret),   reinterpret_cast<int2 *>(ekids),
-                           reinterpret_cast<int *>(kid),       reinterpret_cast<uint32_t *>(tsum),
-                           reinterpret_cast<uint64_t *>(toff), reinterpret_cast<int *>(tnodes),
-                           reinterpret_cast<int *>(tleaf),     reinterpret_cast<float *>(txyz),
-                           build,                              bb};
-    return at;
+    MergeScratch m{};
+    m.build_bytes = gsr_hier_build_scratch_bytes(C);
+    m.ctl = cv.take<uint64_t>(64);
+    m.first = cv.take<int64_t>(8 * (c + 1));
+    m.kc = cv.take<uint64_t>(8 * c);
+    m.root = cv.take<int>(4 * c);
+    m.active = cv.take<int>(4 * c);
+    m.flag = cv.take<uint32_t>(4 * t);
+    m.ret = cv.take<uint8_t>(t);
+    m.ekids = cv.take<int2>(8 * t);
+    m.kid = cv.take<int>(4 * (t + c));
+    m.tile_sum = cv.take<uint32_t>(4 * nt);
+    m.tile_off = cv.take<uint64_t>(8 * nt);
+    m.tnodes = cv.take<int>(28 * (2 * c - 1));
+    m.tleaf = cv.take<int>(4 * (2 * c - 1));
+    m.txyz = cv.take<float>(12 * c);
+    m.build = cv.take(m.build_bytes);
+    if (sc) *sc = m;
+    return cv.off;
 }
 
 HierRows top_rows_of(float *top, int64_t C, int M) {

@@ -22,6 +22,7 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_knn.h"
+#include "grid_cell.h"  // f2ord / ord2f, wave_minf / wave_maxf, the bounding box's words
 #include "gsr_launch.h"
 
 namespace gsr {
@@ -29,25 +30,6 @@ namespace {
 
 constexpr int kBox = 64;  // points per box = lanes per wave; boxes per superbox
 constexpr int kKnnWaves = 4;
-
-__device__ __forceinline__ uint32_t f2ord(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
-__device__ __forceinline__ float wave_minf(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_maxf(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 
 // simple-knn's updateKBest<3>: insertion into the ascending best list (strict >)
 __device__ __forceinline__ void update3(float d, float &b0, float &b1, float &b2) {
@@ -69,36 +51,7 @@ __device__ __forceinline__ float box_dist(const float4 &amin, const float4 &amax
                gap(amin.z, amax.z, bmin.z, bmax.z));
 }
 
-__global__ __launch_bounds__(256) void knn_bbox_kernel(int64_t N, const float *__restrict__ p, uint32_t *bb) {
-    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float v = p[3 * i + k];
-            mn[k] = fminf(mn[k], v);
-            mx[k] = fmaxf(mx[k], v);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        mn[k] = wave_minf(mn[k]);
-        mx[k] = wave_maxf(mx[k]);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            atomicMin(&bb[k], f2ord(mn[k]));
-            atomicMax(&bb[3 + k], f2ord(mx[k]));
-        }
-    }
-}
-
-__global__ void knn_bbox_init_kernel(uint32_t *bb) {
-    if (threadIdx.x < 3) {
-        bb[threadIdx.x] = 0xffffffffu;
-        bb[3 + threadIdx.x] = 0u;
-    }
-}
+__global__ void knn_bbox_init_kernel(uint32_t *bb) { bbox_words_init(bb); }
 
 __device__ __forceinline__ uint32_t spread10(uint32_t x) {  // 10 bits -> every third bit
     x &= 0x3ffu;
@@ -245,23 +198,18 @@ struct KnnLayout {
 KnnLayout knn_layout(char *base, int64_t N) {
     KnnLayout L{};
     const int64_t nb = (N + kBox - 1) / kBox, nsb = (nb + kBox - 1) / kBox;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off = align_up(off + bytes, 256);
-        return p;
-    };
-    L.bb = reinterpret_cast<uint32_t *>(take(8 * sizeof(uint32_t)));
-    L.key = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * N));
-    L.key_s = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * N));
-    L.idx = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * N));
-    L.idx_s = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * N));
-    L.pts = reinterpret_cast<float4 *>(take(sizeof(float4) * N));
-    L.boxes = reinterpret_cast<float4 *>(take(sizeof(float4) * 2 * nb));
-    L.sboxes = reinterpret_cast<float4 *>(take(sizeof(float4) * 2 * nsb));
+    Carve c(base);
+    L.bb = c.take<uint32_t>(kBBoxWords * sizeof(uint32_t));
+    L.key = c.take<uint32_t>(sizeof(uint32_t) * N);
+    L.key_s = c.take<uint32_t>(sizeof(uint32_t) * N);
+    L.idx = c.take<uint32_t>(sizeof(uint32_t) * N);
+    L.idx_s = c.take<uint32_t>(sizeof(uint32_t) * N);
+    L.pts = c.take<float4>(sizeof(float4) * N);
+    L.boxes = c.take<float4>(sizeof(float4) * 2 * nb);
+    L.sboxes = c.take<float4>(sizeof(float4) * 2 * nsb);
     L.tmp_bytes = sort_pairs_temp_bytes((size_t)N, 30);
-    L.tmp = take(L.tmp_bytes);
-    L.total = off;
+    L.tmp = c.take(L.tmp_bytes);
+    L.total = c.off;
     return L;
 }
 
@@ -288,7 +236,7 @@ int gsr_knn_mean_dist2(int64_t N, const float *points, float *out, void *scratch
     const int64_t nb = (N + kBox - 1) / kBox, nsb = (nb + kBox - 1) / kBox;
     hipLaunchKernelGGL(knn_bbox_init_kernel, dim3(1), dim3(64), 0, s, L.bb);
     const int64_t gb = (N + 255) / 256;
-    hipLaunchKernelGGL(knn_bbox_kernel, dim3((unsigned)(gb < 2048 ? gb : 2048)), dim3(256), 0, s, N, points, L.bb);
+    launch_bbox(N, points, nullptr, L.bb, s, 2048);
     hipLaunchKernelGGL(knn_morton_kernel, dim3((unsigned)gb), dim3(256), 0, s, N, points, L.bb, L.key, L.idx);
     const hipError_t e = sort_pairs(L.tmp, L.tmp_bytes, L.key, L.key_s, L.idx, L.idx_s, (size_t)N, 30, s);
     if (e != hipSuccess) {

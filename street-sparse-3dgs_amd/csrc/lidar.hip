@@ -12,32 +12,29 @@
 //          gathered as nine floats per reference: a cell is one contiguous run.  A triangle whose grown
 //          box covers more than kMaxCells cells writes ONE pair under the key past the last cell, so
 //          the sort leaves those triangles as the last run: the oversize list.
-//   query: a lane per point.  crop, then the point's own cell (one binary search of the cell table; a
-//          range of cells when max_distance exceeds the one the index was built for, the cells
-//          x0..x1 of a (y, z) row being one run as in gtcloud.hip), runs of up to kLaneRun
-//          references scanned by the lane, longer ones by the wave with the owner's point broadcast,
-//          leaving a run at the first triangle in range; then the oversize list, read at
-//          wave-uniform addresses by the lanes still without a triangle.
+//   query: a lane per point.  crop, then grid_cell.h's cell_walk over the point's own cell (a range of
+//          cells when max_distance exceeds the one the index was built for) with near() as the
+//          predicate; then the oversize list, read at wave-uniform addresses by the lanes still
+//          without a triangle.
 //   voxel mean: ordered-integer bounding box of the kept points, one 64-bit key (iz, iy, ix) per point
 //          (dropped points get the key past every voxel), the stable pair sort, key_runs, and one
 //          lane per voxel summing its points in fp64 in input order; voxels longer than kLaneRun are
 //          taken by the wave: lane l sums points l, l + 64, ... in order, then a butterfly adds the 64
 //          partial sums.  No atomics on floats anywhere, so the output is a function of the input.
 //
-// Exactness of the grid.  near() holds only when !sep: on every axis some vertex v
-// has rn(v - p) < reach and some vertex has rn(v - p) > -reach, hence (one rounding, monotone)
-// min_k - reach (1 + 2^-23) <= p_k <= max_k + reach (1 + 2^-23) as real numbers.  The build grows the
-// box by reach_b >= reach (1 + 2^-20) and steps the fp32 results outward (nextafter), so lo_k <= p_k
-// <= hi_k, and cell_of is monotone and the same function for both: cell_of(lo_k) <= cell_of(p_k) <=
-// cell_of(hi_k): the point's own cell lists the triangle.  For a larger query reach the point searches
+// Exactness of the grid (grid_cell.h has the part shared with gtcloud.hip).  near()
+// holds only when !sep: on every axis some vertex v has rn(v - p) < reach and some vertex has
+// rn(v - p) > -reach, hence (one rounding, monotone) min_k - reach (1 + 2^-23) <= p_k <=
+// max_k + reach (1 + 2^-23) as real numbers.  The build grows the box by reach_b >= reach (1 + 2^-20)
+// and steps the fp32 results outward (nextafter), so lo_k <= p_k <= hi_k, and cell_of is monotone and
+// the same function for both: cell_of(lo_k) <= cell_of(p_k) <= cell_of(hi_k): the point's own cell
+// lists the triangle.  For a larger query reach the point searches
 // [cell_of(below(p - e)), cell_of(above(p + e))] with e >= reach_q (1 + 2^-20) - reach_b, which meets
-// the triangle's cell range on every axis by the same argument.  Every listed triangle is tested by
-// near() itself, a triangle listed twice changes nothing, so the mask equals the all-pairs result.
+// the triangle's cell range on every axis by the same argument.
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstring>
 #include <string>
-#include <vector>
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_lidar.h"
@@ -46,16 +43,10 @@
 
 namespace gsr {
 
-// what the kernels need of a mesh index
-struct MeshGrid {
-    const float *tri;            // nine floats per reference, cell order, the oversize list last
-    const uint64_t *cell_key;    // ascending keys of the occupied cells
-    const uint32_t *cell_start;  // n_cells + 1: first reference of each cell, then over_start
-    uint32_t n_cells;
+// what the kernels need of a mesh index: cell_start[n_cells] = over_start
+struct MeshGrid : CellGrid {
+    const float *tri;               // nine floats per reference, cell order, the oversize list last
     uint32_t over_start, over_end;  // the oversize list as references [over_start, over_end)
-    float lo[3], hi[3];             // the vertices' fp32 bounding box
-    float inv_h;
-    int32_t n[3];  // cells per axis
 };
 
 }  // namespace gsr
@@ -75,50 +66,16 @@ namespace gsr {
 namespace {
 
 constexpr uint64_t kMeshMagic = 0x6773725f6d657368ull;  // "gsr_mesh"
-constexpr uint32_t kLaneRun = 16;    // longer runs are shared by the wave
 constexpr uint64_t kMaxCells = 512;  // a triangle covering more cells goes to the oversize list
 constexpr uint32_t kSideSteps = 65536;
 
 // ---- the mesh index ----------------------------------------------------------------------------
 
-// words: 0..2 ordered min, 3..5 ordered max, 6 flags (1: non-finite vertex, 2: face index out of range)
-__global__ void mesh_words_init_kernel(uint32_t *w, unsigned long long *sums) {
-    if (threadIdx.x < 3) {
-        w[threadIdx.x] = 0xffffffffu;
-        w[3 + threadIdx.x] = 0u;
-    }
-    if (threadIdx.x == 3) w[6] = 0u;
-    if (threadIdx.x < 2) sums[threadIdx.x] = 0ull;
-}
+constexpr uint32_t kMeshBadFace = 2u;  // beside kBBoxNonFinite in the flag word: a face index out of range
 
-__global__ __launch_bounds__(256) void mesh_bbox_kernel(int64_t V, const float *__restrict__ p, uint32_t *w) {
-    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    bool bad = false;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (int64_t)gridDim.x * blockDim.x) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float v = p[3 * i + k];
-            bad |= !isfinite(v);
-            mn[k] = fminf(mn[k], v);
-            mx[k] = fmaxf(mx[k], v);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[k] = fminf(mn[k], __shfl_xor(mn[k], o));
-            mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o));
-        }
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&w[6], 1u);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            atomicMin(&w[k], f2ord(mn[k]));
-            atomicMax(&w[3 + k], f2ord(mx[k]));
-        }
-    }
+__global__ void mesh_words_init_kernel(uint32_t *w, unsigned long long *sums) {
+    bbox_words_init(w);
+    if (threadIdx.x < 2) sums[threadIdx.x] = 0ull;
 }
 
 // the nine floats of triangle t; false when a face index is out of range (nothing is read then)
@@ -156,7 +113,7 @@ __global__ __launch_bounds__(256) void mesh_side_kernel(int64_t V, const float *
             bad = true;
         }
     }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&w[6], 2u);
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&w[kBBoxFlags], kMeshBadFace);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
     if ((threadIdx.x & 63) == 0 && q) atomicAdd(&sums[0], (unsigned long long)q);
@@ -180,10 +137,6 @@ __device__ __forceinline__ TriCells tri_cells(const float v[9], const MeshGrid &
         c.n *= (uint64_t)(c.c1[k] - c.c0[k] + 1);
     }
     return c;
-}
-
-__device__ __forceinline__ uint64_t mesh_key_of(int cx, int cy, int cz, const MeshGrid &g) {
-    return ((uint64_t)cz * (uint64_t)g.n[1] + (uint64_t)cy) * (uint64_t)g.n[0] + (uint64_t)cx;
 }
 
 // count: the pairs triangle t writes (1 for an oversize one); sums[1]: their total
@@ -228,7 +181,7 @@ __global__ __launch_bounds__(256) void mesh_fill_kernel(int64_t V, const float *
         for (int cy = tc.c0[1]; cy <= tc.c1[1]; cy++)
             for (int cx = tc.c0[0]; cx <= tc.c1[0]; cx++, j++) {
                 if (j >= R) return;  // cannot happen: the same function counted the cells
-                key[j] = mesh_key_of(cx, cy, cz, g);
+                key[j] = cell_key_of(cx, cy, cz, g);
                 val[j] = (uint32_t)t;
             }
 }
@@ -313,7 +266,6 @@ __global__ __launch_bounds__(256) void mesh_near_mask_kernel(int64_t P, const fl
                                                              int has_index, float T, float reach, float ext, CropBox box,
                                                              uint8_t *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     float q[3] = {0.f, 0.f, 0.f};
     if (i < P) {
         q[0] = xyz[3 * i];
@@ -327,7 +279,7 @@ __global__ __launch_bounds__(256) void mesh_near_mask_kernel(int64_t P, const fl
         return;
     }
     if (!ok) q[0] = q[1] = q[2] = 0.f;
-    bool search = ok, near = false;
+    bool search = ok;
     int c0[3], c1[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -339,48 +291,9 @@ __global__ __launch_bounds__(256) void mesh_near_mask_kernel(int64_t P, const fl
         c0[k] = cell_of(lo, g.lo[k], g.inv_h, g.n[k]);
         c1[k] = cell_of(hi, g.lo[k], g.inv_h, g.n[k]);
     }
-    const int64_t ny = c1[1] - c0[1] + 1;
-    const int64_t nrows = search ? ny * (int64_t)(c1[2] - c0[2] + 1) : 0;
-    for (int64_t r = 0; __any(r < nrows && !near); r++) {
-        uint32_t s = 0, e = 0;
-        if (r < nrows && !near) {
-            const int cz = c0[2] + (int)(r / ny), cy = c0[1] + (int)(r % ny);
-            const uint64_t k0 = mesh_key_of(c0[0], cy, cz, g), k1 = mesh_key_of(c1[0], cy, cz, g);
-            uint32_t a = 0, b = g.n_cells;
-            while (a < b) {  // the first occupied cell with key >= k0
-                const uint32_t m = (a + b) >> 1;
-                if (g.cell_key[m] < k0) a = m + 1;
-                else b = m;
-            }
-            uint32_t j = a;
-            while (j < g.n_cells && g.cell_key[j] <= k1) j++;
-            s = g.cell_start[a];  // cell_start[n_cells] = over_start
-            e = g.cell_start[j];
-        }
-        if (e - s <= kLaneRun) {
-            for (uint32_t j = s; j < e; j++) {
-                if (tri_near(g.tri + 9 * (size_t)j, q[0], q[1], q[2], T, reach)) {
-                    near = true;
-                    break;
-                }
-            }
-            s = e;
-        }
-        unsigned long long pending = __ballot(e > s);
-        while (pending) {
-            const int l = __ffsll((long long)pending) - 1;
-            pending &= pending - 1;
-            const float bx = __shfl(q[0], l), by = __shfl(q[1], l), bz = __shfl(q[2], l);
-            const uint32_t bs = (uint32_t)__shfl((int)s, l), be = (uint32_t)__shfl((int)e, l);
-            bool hit = false;
-            for (uint32_t j = bs; j < be && !hit; j += 64) {
-                const uint32_t jj = j + lane;
-                const bool h = jj < be && tri_near(g.tri + 9 * (size_t)jj, bx, by, bz, T, reach);
-                hit = __any(h);
-            }
-            if (hit && lane == l) near = true;
-        }
-    }
+    bool near = cell_walk(g, c0, c1, search, q[0], q[1], q[2], [&](uint32_t j, float x, float y, float z) {
+        return tri_near(g.tri + 9 * (size_t)j, x, y, z, T, reach);
+    });
     // the oversize list: the same triangle for every lane of the wave
     for (uint32_t j = g.over_start; j < g.over_end && __any(search && !near); j++)
         if (search && !near && tri_near(g.tri + 9 * (size_t)j, q[0], q[1], q[2], T, reach)) near = true;
@@ -396,49 +309,10 @@ struct VoxGrid {
     uint64_t drop_key;    // 1 << (bits of all three): sorts after every voxel
 };
 
-// words: 0..2 ordered min, 3..5 ordered max, 6 kept points, 7 flag (a kept point is not finite)
+// the words of launch_bbox over the kept points, then 8: the number of voxels (key_runs)
 __global__ void vox_words_init_kernel(uint32_t *w) {
-    if (threadIdx.x < 3) {
-        w[threadIdx.x] = 0xffffffffu;
-        w[3 + threadIdx.x] = 0u;
-    }
-    if (threadIdx.x >= 6 && threadIdx.x < 9) w[threadIdx.x] = 0u;  // 8: the number of voxels (key_runs)
-}
-
-__global__ __launch_bounds__(256) void vox_bbox_kernel(int64_t P, const float *__restrict__ p,
-                                                       const uint8_t *__restrict__ keep, uint32_t *w) {
-    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    uint32_t kept = 0;
-    bool bad = false;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x) {
-        if (keep != nullptr && keep[i] == 0) continue;
-        kept++;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float v = p[3 * i + k];
-            bad |= !isfinite(v);
-            mn[k] = fminf(mn[k], v);
-            mx[k] = fmaxf(mx[k], v);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        kept += __shfl_xor(kept, o);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            mn[k] = fminf(mn[k], __shfl_xor(mn[k], o));
-            mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o));
-        }
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&w[7], 1u);
-    if ((threadIdx.x & 63) == 0 && kept) {
-        atomicAdd(&w[6], kept);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            atomicMin(&w[k], f2ord(mn[k]));
-            atomicMax(&w[3 + k], f2ord(mx[k]));
-        }
-    }
+    bbox_words_init(w);
+    if (threadIdx.x == 8) w[8] = 0u;
 }
 
 // the voxel coordinate along one axis (gsr_lidar.h): fp64, every operation rounded once
@@ -520,8 +394,6 @@ __global__ __launch_bounds__(256) void vox_mean_kernel(uint32_t n_runs, uint32_t
     }
 }
 
-size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct VoxScratch {
     uint64_t *key_in, *key_out;  // key_in is the voxels' keys after the sort
     uint32_t *idx_in, *idx_out;  // idx_in is the voxels' first positions after the sort
@@ -532,21 +404,16 @@ struct VoxScratch {
 
 VoxScratch vox_carve(void *base, size_t P) {
     VoxScratch v{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? static_cast<char *>(base) + off : nullptr;
-        off += align_up(bytes);
-        return static_cast<void *>(p);
-    };
-    v.key_in = static_cast<uint64_t *>(take(P * 8));
-    v.key_out = static_cast<uint64_t *>(take(P * 8));
-    v.idx_in = static_cast<uint32_t *>(take(P * 4));
-    v.idx_out = static_cast<uint32_t *>(take(P * 4));
-    v.words = static_cast<uint32_t *>(take(64));
+    Carve c(base);
+    v.key_in = c.take<uint64_t>(P * 8);
+    v.key_out = c.take<uint64_t>(P * 8);
+    v.idx_in = c.take<uint32_t>(P * 4);
+    v.idx_out = c.take<uint32_t>(P * 4);
+    v.words = c.take<uint32_t>(64);
     const size_t a = sort_pairs64_temp_bytes(P, 64), b = key_runs_temp_bytes(P);
     v.tmp_bytes = a > b ? a : b;
-    v.tmp = take(v.tmp_bytes);
-    v.total = off;
+    v.tmp = c.take(v.tmp_bytes);
+    v.total = c.off;
     return v;
 }
 
@@ -554,12 +421,6 @@ bool mesh_grid_of(const gsr_mesh_index *ix, MeshGrid *out) {
     if (!ix || ix->magic != kMeshMagic) return false;
     *out = ix->grid;
     return true;
-}
-
-int bits_for(uint64_t n) {  // bits that hold 0 .. n - 1
-    int b = 0;
-    while (b < 64 && ((n - 1) >> b) != 0) b++;
-    return b;
 }
 
 }  // namespace
@@ -583,176 +444,90 @@ gsr_mesh_index *gsr_mesh_index_create(int64_t V, const float *vertices, int64_t 
     float reach_b = (float)rb;
     if ((double)reach_b < rb) reach_b = std::nextafterf(reach_b, INFINITY);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    std::vector<void *> held;
-    auto drop_all = [&]() {
-        for (void *p : held) (void)hipFree(p);
-        held.clear();
-    };
-    auto fail = [&](const std::string &what, hipError_t e) {
-        drop_all();
-        set_last_error("gsr_mesh_index_create: " + what + ": " + hipGetErrorString(e));
-        return static_cast<gsr_mesh_index *>(nullptr);
-    };
-    auto reject = [&](const std::string &what) {
-        drop_all();
-        set_last_error("gsr_mesh_index_create: " + what);
-        return static_cast<gsr_mesh_index *>(nullptr);
-    };
-    auto alloc = [&](size_t bytes, hipError_t *e) {
-        void *p = nullptr;
-        *e = hipMalloc(&p, bytes ? bytes : 1);
-        if (*e == hipSuccess) held.push_back(p);
-        return p;
-    };
-    auto release = [&](void *p) {
-        for (auto &h : held)
-            if (h == p) {
-                (void)hipFree(p);
-                h = held.back();
-                held.pop_back();
-                return;
-            }
-    };
-    hipError_t e;
-    const unsigned vblocks = (unsigned)(((size_t)V + 255) / 256), fblocks = (unsigned)(((size_t)F + 255) / 256);
+    const char *who = "gsr_mesh_index_create";
+    DeviceBufs bufs;
+    const unsigned fblocks = (unsigned)(((size_t)F + 255) / 256);
 
     // 1. the vertices' bounding box, the face indices, the triangles' mean side
-    uint32_t *words = static_cast<uint32_t *>(alloc(8 * sizeof(uint32_t), &e));
-    if (e != hipSuccess) return fail("allocation", e);
-    unsigned long long *sums = static_cast<unsigned long long *>(alloc(2 * sizeof(unsigned long long), &e));
-    if (e != hipSuccess) return fail("allocation", e);
+    uint32_t *words = bufs.alloc<uint32_t>(kBBoxWords);
+    unsigned long long *sums = bufs.alloc<unsigned long long>(2);
+    if (bufs.error() != hipSuccess) return build_stopped(who, {"allocation", bufs.error()});
     const float cap = 8.f * reach_b;
-    if (!std::isfinite(cap)) return reject("max_distance out of the fp32 range");
+    if (!std::isfinite(cap)) return build_stopped(who, {"max_distance out of the fp32 range"});
     hipLaunchKernelGGL(mesh_words_init_kernel, dim3(1), dim3(64), 0, s, words, sums);
-    hipLaunchKernelGGL(mesh_bbox_kernel, dim3(vblocks < 1024u ? vblocks : 1024u), dim3(256), 0, s, V, vertices, words);
+    launch_bbox(V, vertices, nullptr, words, s);
     hipLaunchKernelGGL(mesh_side_kernel, dim3(fblocks), dim3(256), 0, s, V, vertices, F, faces, cap, words, sums);
-    uint32_t hw[8];
+    uint32_t hw[kBBoxWords];
     unsigned long long hs[2];
-    e = hipMemcpyAsync(hw, words, sizeof(hw), hipMemcpyDeviceToHost, s);
+    hipError_t e = hipMemcpyAsync(hw, words, sizeof(hw), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(hs, sums, sizeof(hs), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail("bounding box", e);
-    if (hw[6] & 1u) return reject("the mesh has a vertex with a NaN or Inf coordinate");
-    if (hw[6] & 2u) return reject("a face index is out of range (0 <= index < V)");
+    if (e != hipSuccess) return build_stopped(who, {"bounding box", e});
+    if (hw[kBBoxFlags] & kBBoxNonFinite)
+        return build_stopped(who, {"the mesh has a vertex with a NaN or Inf coordinate"});
+    if (hw[kBBoxFlags] & kMeshBadFace) return build_stopped(who, {"a face index is out of range (0 <= index < V)"});
     MeshGrid g{};
     float ext = 0.f;
-    for (int k = 0; k < 3; k++) {
-        g.lo[k] = ord2f(hw[k]);
-        g.hi[k] = ord2f(hw[3 + k]);
-        if (!std::isfinite(g.lo[k]) || !std::isfinite(g.hi[k]) || !std::isfinite(g.hi[k] - g.lo[k]))
-            return reject("the mesh's extent is out of the fp32 range");
-        ext = fmaxf(ext, g.hi[k] - g.lo[k]);
-    }
+    if (!cell_grid_box(&g, hw, &ext)) return build_stopped(who, {"the mesh's extent is out of the fp32 range"});
     // 2. the grid: edge >= 2 reach and about a triangle's side, at most 2^20 + 2 cells per axis
     const float mean_side = (float)((double)cap * (double)hs[0] / ((double)kSideSteps * (double)F));
-    const float h = fmaxf(fmaxf(2.f * reach_b, mean_side), ext / 1048576.f);
-    g.inv_h = 1.f / h;
-    if (!std::isfinite(g.inv_h) || !(g.inv_h > 0.f)) return reject("cell edge out of the fp32 range");
     uint64_t cells = 1;
-    for (int k = 0; k < 3; k++) {
-        const float t = floorf((g.hi[k] - g.lo[k]) * g.inv_h);
-        g.n[k] = (int32_t)fminf(fmaxf(t, 0.f), 2097150.f) + 1;
-        cells *= (uint64_t)g.n[k];
-    }
+    if (!cell_grid_dims(&g, fmaxf(fmaxf(2.f * reach_b, mean_side), ext / 1048576.f), &cells))
+        return build_stopped(who, {"cell edge out of the fp32 range"});
     const uint64_t over_key = cells;  // past every cell's key
-    const int end_bit = bits_for(cells + 1) < 1 ? 1 : bits_for(cells + 1);
+    const int end_bit = std::max(1, bits_for(cells + 1));
 
     // 3. count, scan, fill
-    uint32_t *cnt = static_cast<uint32_t *>(alloc((size_t)F * 4, &e));
-    if (e != hipSuccess) return fail("allocation", e);
-    uint32_t *off = static_cast<uint32_t *>(alloc((size_t)F * 4, &e));
-    if (e != hipSuccess) return fail("allocation", e);
+    uint32_t *cnt = bufs.alloc<uint32_t>((size_t)F);
+    uint32_t *off = bufs.alloc<uint32_t>((size_t)F);
+    if (bufs.error() != hipSuccess) return build_stopped(who, {"allocation", bufs.error()});
     hipLaunchKernelGGL(mesh_count_kernel, dim3(fblocks), dim3(256), 0, s, V, vertices, F, faces, g, reach_b, cnt, sums);
     e = hipMemcpyAsync(hs, sums, sizeof(hs), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail("count", e);
-    if (hs[1] < 1 || hs[1] >= (1ull << 31)) return reject("the index would hold more than 2^31 - 1 triangle references");
+    if (e != hipSuccess) return build_stopped(who, {"count", e});
+    if (hs[1] < 1 || hs[1] >= (1ull << 31))
+        return build_stopped(who, {"the index would hold more than 2^31 - 1 triangle references"});
     const uint32_t R = (uint32_t)hs[1];
     const unsigned rblocks = (unsigned)(((size_t)R + 255) / 256);
-    size_t tmp_bytes = scan_u32_temp_bytes((size_t)F);
-    void *tmp = alloc(tmp_bytes, &e);
-    if (e != hipSuccess) return fail("allocation", e);
+    const size_t tmp_bytes = scan_u32_temp_bytes((size_t)F);
+    void *tmp = bufs.alloc<char>(tmp_bytes);
+    if (bufs.error() != hipSuccess) return build_stopped(who, {"allocation", bufs.error()});
     e = scan_u32(tmp, tmp_bytes, cnt, off, (size_t)F, s);
-    if (e != hipSuccess) return fail("scan", e);
-    uint64_t *key_in = static_cast<uint64_t *>(alloc((size_t)R * 8, &e));
-    if (e != hipSuccess) return fail("allocation", e);
-    uint64_t *key = static_cast<uint64_t *>(alloc((size_t)R * 8, &e));
-    if (e != hipSuccess) return fail("allocation", e);
-    uint32_t *val_in = static_cast<uint32_t *>(alloc((size_t)R * 4, &e));
-    if (e != hipSuccess) return fail("allocation", e);
-    uint32_t *val = static_cast<uint32_t *>(alloc((size_t)R * 4, &e));
-    if (e != hipSuccess) return fail("allocation", e);
+    if (e != hipSuccess) return build_stopped(who, {"scan", e});
+    uint64_t *key_in = bufs.alloc<uint64_t>(R);
+    uint32_t *val_in = bufs.alloc<uint32_t>(R);
+    if (bufs.error() != hipSuccess) return build_stopped(who, {"allocation", bufs.error()});
     e = hipMemsetAsync(val_in, 0, (size_t)R * 4, s);  // every slot is written below; a triangle number in any case
-    if (e != hipSuccess) return fail("fill", e);
+    if (e != hipSuccess) return build_stopped(who, {"fill", e});
     hipLaunchKernelGGL(mesh_fill_kernel, dim3(fblocks), dim3(256), 0, s, V, vertices, F, faces, g, reach_b, over_key, off,
                        R, key_in, val_in);
     e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail("fill", e);
-    release(tmp);
-    release(cnt);
-    release(off);
+    if (e != hipSuccess) return build_stopped(who, {"fill", e});
+    bufs.release(tmp);
+    bufs.release(cnt);
+    bufs.release(off);
 
     // 4. cell order (stable: ascending triangle numbers inside a cell), the triangles, the cell table
-    tmp_bytes = sort_pairs64_temp_bytes(R, end_bit);
-    tmp = alloc(tmp_bytes, &e);
-    if (e != hipSuccess) return fail("allocation", e);
-    e = sort_pairs64(tmp, tmp_bytes, key_in, key, val_in, val, R, end_bit, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail("sort", e);
-    release(tmp);
-    release(key_in);
-    release(val_in);
-    float *tri = static_cast<float *>(alloc((size_t)R * 9 * sizeof(float), &e));
-    if (e != hipSuccess) return fail("allocation", e);
-    hipLaunchKernelGGL(mesh_gather_kernel, dim3(rblocks), dim3(256), 0, s, V, vertices, faces, R, val, tri);
-    uint64_t *run_key = static_cast<uint64_t *>(alloc((size_t)R * 8, &e));
-    if (e != hipSuccess) return fail("allocation", e);
-    uint32_t *run_start = static_cast<uint32_t *>(alloc((size_t)R * 4, &e));
-    if (e != hipSuccess) return fail("allocation", e);
-    uint32_t *n_runs = static_cast<uint32_t *>(alloc(4, &e));
-    if (e != hipSuccess) return fail("allocation", e);
-    tmp_bytes = key_runs_temp_bytes(R);
-    tmp = alloc(tmp_bytes, &e);
-    if (e != hipSuccess) return fail("allocation", e);
-    e = key_runs(tmp, tmp_bytes, key, R, run_key, run_start, n_runs, s);
-    uint32_t nc = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&nc, n_runs, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail("cell table", e);
-    if (nc < 1 || nc > R) return reject("cell table: impossible cell count");
-    uint64_t last_key = 0;
-    uint32_t last_start = 0;
-    e = hipMemcpyAsync(&last_key, run_key + (nc - 1), 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&last_start, run_start + (nc - 1), 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail("cell table", e);
-    release(tmp);
-    release(key);
-    release(val);
-    release(n_runs);
-    uint64_t *cell_key = static_cast<uint64_t *>(alloc((size_t)nc * 8, &e));
-    if (e != hipSuccess) return fail("allocation", e);
-    uint32_t *cell_start = static_cast<uint32_t *>(alloc(((size_t)nc + 1) * 4, &e));
-    if (e != hipSuccess) return fail("allocation", e);
-    e = hipMemcpyAsync(cell_key, run_key, (size_t)nc * 8, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(cell_start, run_start, (size_t)nc * 4, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(cell_start + nc, &R, 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return fail("cell table copy", e);
-    release(run_key);
-    release(run_start);
-    release(words);
-    release(sums);
+    CellTable t;
+    if (const BuildStop stop = sort_cell_pairs(bufs, key_in, val_in, R, end_bit, s, &t))
+        return build_stopped(who, stop);
+    float *tri = bufs.alloc<float>((size_t)R * 9);
+    if (bufs.error() != hipSuccess) return build_stopped(who, {"allocation", bufs.error()});
+    hipLaunchKernelGGL(mesh_gather_kernel, dim3(rblocks), dim3(256), 0, s, V, vertices, faces, R, t.values, tri);
+    if (const BuildStop stop = finish_cell_table(bufs, R, true, s, &t)) return build_stopped(who, stop);
+    bufs.release(words);
+    bufs.release(sums);
+    bufs.disown();
 
     // the oversize list is the run under over_key, the last one: the cell table ends before it, and
     // cell_start[n_cells] is then its first reference
-    const bool has_over = last_key == over_key;
+    const uint32_t nc = t.n_cells;
+    const bool has_over = t.last_key == over_key;
     g.tri = tri;
-    g.cell_key = cell_key;
-    g.cell_start = cell_start;
+    g.cell_key = t.cell_key;
+    g.cell_start = t.cell_start;
     g.n_cells = has_over ? nc - 1 : nc;
-    g.over_start = has_over ? last_start : R;
+    g.over_start = has_over ? t.last_start : R;
     g.over_end = R;
     gsr_mesh_index *ix = new gsr_mesh_index{};
     ix->magic = kMeshMagic;
@@ -763,8 +538,8 @@ gsr_mesh_index *gsr_mesh_index_create(int64_t V, const float *vertices, int64_t 
     ix->bytes = (size_t)R * 9 * sizeof(float) + (size_t)nc * 8 + ((size_t)nc + 1) * 4;
     ix->reach_b = reach_b;
     ix->tri = tri;
-    ix->cell_key = cell_key;
-    ix->cell_start = cell_start;
+    ix->cell_key = t.cell_key;
+    ix->cell_start = t.cell_start;
     return ix;
 }
 
@@ -838,17 +613,16 @@ int gsr_voxel_mean(int64_t P, const float *xyz, const float *colors, const uint8
 
     // 1. the kept points' bounding box (exact in fp32, widened below) and their number
     hipLaunchKernelGGL(vox_words_init_kernel, dim3(1), dim3(64), 0, s, sc.words);
-    hipLaunchKernelGGL(vox_bbox_kernel, dim3(blocks < 1024u ? blocks : 1024u), dim3(256), 0, s, P, xyz, keep_mask,
-                       sc.words);
-    uint32_t hw[8];
+    launch_bbox(P, xyz, keep_mask, sc.words, s);
+    uint32_t hw[kBBoxWords];
     hipError_t e = hipMemcpyAsync(hw, sc.words, sizeof(hw), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return device_error("bounding box", e);
-    if (hw[7]) {
+    if (hw[kBBoxFlags]) {
         set_last_error("gsr_voxel_mean: a kept point has a NaN or Inf coordinate");
         return GSR_ERR_INVALID_ARGUMENT;
     }
-    const uint32_t K = hw[6];
+    const uint32_t K = hw[kBBoxKept];
     if (K == 0) return GSR_OK;
 
     // 2. the voxel grid and the key layout

@@ -107,21 +107,15 @@ struct CutScratch {
 __host__ __device__ inline int64_t cut_groups(int64_t ntiles) { return (ntiles + kCutGroup - 1) / kCutGroup; }
 
 __host__ __device__ inline size_t cut_scratch_bytes(int64_t ntiles, CutScratch *sc, char *base) {
-    size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at = align_up(at + bytes, 256);
-        return base ? base + o : nullptr;
-    };
-    char *ctl = take(sizeof(uint64_t) * (size_t)(kCutHead + cut_groups(ntiles)));
-    char *sum = take(sizeof(uint32_t) * (size_t)ntiles);
-    char *nrec = take(sizeof(uint32_t) * (size_t)ntiles);
-    char *goff = take(sizeof(uint64_t) * (size_t)cut_groups(ntiles));
-    char *recs = take(sizeof(uint4) * (size_t)ntiles * kCutTile);
-    if (sc) *sc = CutScratch{reinterpret_cast<uint64_t *>(ctl), reinterpret_cast<uint32_t *>(sum),
-                             reinterpret_cast<uint32_t *>(nrec), reinterpret_cast<uint64_t *>(goff),
-                             reinterpret_cast<uint4 *>(recs)};
-    return at;
+    Carve c(base);
+    CutScratch t{};
+    t.ctl = c.take<uint64_t>(sizeof(uint64_t) * (size_t)(kCutHead + cut_groups(ntiles)));
+    t.tile_sum = c.take<uint32_t>(sizeof(uint32_t) * (size_t)ntiles);
+    t.tile_nrec = c.take<uint32_t>(sizeof(uint32_t) * (size_t)ntiles);
+    t.group_off = c.take<uint64_t>(sizeof(uint64_t) * (size_t)cut_groups(ntiles));
+    t.recs = c.take<uint4>(sizeof(uint4) * (size_t)ntiles * kCutTile);
+    if (sc) *sc = t;
+    return c.off;
 }
 
 __global__ __launch_bounds__(kCutThreads) void lod_cut_count_kernel(int64_t N, int64_t ntiles, const int *__restrict__ nodes,

@@ -33,6 +33,7 @@
 // misses changes nothing, so the map equals the all-pairs one wherever the rule's own rounding at a
 // triangle's edge is below a pixel (it is 2^-24 distance fx / edge length pixels: a millimetre edge at
 // 60 m under fx = 256).
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <string>
@@ -478,8 +479,6 @@ __global__ __launch_bounds__(256) void enc_write_kernel(int64_t npix, const floa
 
 // ---- host ----------------------------------------------------------------------------------------
 
-size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct CastScratch {
     CamRec *cams;
     uint32_t *cnt, *off;
@@ -490,26 +489,15 @@ struct CastScratch {
 
 CastScratch cast_carve(void *base, size_t K, size_t F) {
     CastScratch c{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? static_cast<char *>(base) + o : nullptr;
-        o += align_up(bytes);
-        return static_cast<void *>(p);
-    };
-    c.cams = static_cast<CamRec *>(take(K * sizeof(CamRec)));
-    c.cnt = static_cast<uint32_t *>(take(K * F * 4));
-    c.off = static_cast<uint32_t *>(take(K * F * 4));
-    c.words = static_cast<unsigned long long *>(take(4 * sizeof(unsigned long long)));
+    Carve cv(base);
+    c.cams = cv.take<CamRec>(K * sizeof(CamRec));
+    c.cnt = cv.take<uint32_t>(K * F * 4);
+    c.off = cv.take<uint32_t>(K * F * 4);
+    c.words = cv.take<unsigned long long>(4 * sizeof(unsigned long long));
     c.tmp_bytes = scan_u32_temp_bytes(K * F);
-    c.tmp = take(c.tmp_bytes);
-    c.total = o;
+    c.tmp = cv.take(c.tmp_bytes);
+    c.total = cv.off;
     return c;
-}
-
-int bits_for(uint64_t n) {  // bits that hold 0 .. n - 1
-    int b = 0;
-    while (b < 64 && ((n - 1) >> b) != 0) b++;
-    return b < 1 ? 1 : b;
 }
 
 }  // namespace
@@ -614,11 +602,11 @@ int gsr_mesh_distance_maps(int64_t V, const float *vertices, int64_t F, const in
     }
 
     // 2. scan, fill, sort
-    const int end_bit = bits_for((uint64_t)K * T + (uint64_t)K);
+    const int end_bit = std::max(1, bits_for((uint64_t)K * T + (uint64_t)K));
     const size_t sort_bytes = sort_pairs64_temp_bytes(R, end_bit);
-    const size_t k8 = align_up((size_t)R * 8), v4 = align_up((size_t)R * 4);
+    const size_t k8 = align_up((size_t)R * 8, 256), v4 = align_up((size_t)R * 4, 256);
     char *pairs = nullptr;
-    e = hipMalloc(reinterpret_cast<void **>(&pairs), 2 * k8 + 2 * v4 + align_up(sort_bytes));
+    e = hipMalloc(reinterpret_cast<void **>(&pairs), 2 * k8 + 2 * v4 + align_up(sort_bytes, 256));
     if (e != hipSuccess) {
         drop_events();
         set_last_error(std::string("gsr_mesh_distance_maps: allocation of the references: ") + hipGetErrorString(e));
@@ -665,7 +653,7 @@ int gsr_mesh_distance_maps(int64_t V, const float *vertices, int64_t F, const in
 
 size_t gsr_depth_encode_scratch_bytes(int64_t K) {
     if (K < 1) return 0;
-    return align_up((size_t)K * 16) * 2;
+    return align_up((size_t)K * 16, 256) * 2;
 }
 
 int gsr_depth_encode(int64_t K, int H, int W, const float *distance, int quantize, double min_depth, double max_depth,
@@ -684,7 +672,7 @@ int gsr_depth_encode(int64_t K, int H, int W, const float *distance, int quantiz
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned long long *mm = static_cast<unsigned long long *>(scratch);
-    double *so = reinterpret_cast<double *>(static_cast<char *>(scratch) + align_up((size_t)K * 16));
+    double *so = reinterpret_cast<double *>(static_cast<char *>(scratch) + align_up((size_t)K * 16, 256));
     const int64_t npix = (int64_t)H * W;
     const int64_t want = (npix + 256 * 8 - 1) / (256 * 8);  // about eight pixels a lane
     const unsigned bx = (unsigned)(want < 1 ? 1 : (want > 1024 ? 1024 : want));

@@ -27,6 +27,7 @@
 #include "../../include/gsr.h"
 #include "../../include/gsr_knn.h"
 #include "../../include/gsr_model_init.h"
+#include "grid_cell.h"  // wave_minf / wave_maxf
 #include "gsr_launch.h"
 
 namespace gsr {
@@ -53,29 +54,13 @@ struct InitLayout {
 
 InitLayout init_layout(char *base, int64_t N, int64_t S) {
     InitLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off = align_up(off + bytes, 256);
-        return p;
-    };
-    L.box = reinterpret_cast<BBoxOut *>(take(sizeof(BBoxOut)));
-    L.part = reinterpret_cast<BBoxPart *>(take(sizeof(BBoxPart) * kBBoxBlocks));
-    L.dist2 = reinterpret_cast<float *>(take(sizeof(float) * (size_t)(S + N)));
-    L.knn = take(gsr_knn_scratch_bytes(S + N));
-    L.total = off;
+    Carve c(base);
+    L.box = c.take<BBoxOut>(sizeof(BBoxOut));
+    L.part = c.take<BBoxPart>(sizeof(BBoxPart) * kBBoxBlocks);
+    L.dist2 = c.take<float>(sizeof(float) * (size_t)(S + N));
+    L.knn = c.take(gsr_knn_scratch_bytes(S + N));
+    L.total = c.off;
     return L;
-}
-
-__device__ inline float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ inline float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
 }
 
 // Block reduction of six values (three minima, three maxima): waves, then wave 0 over the waves' values.
@@ -83,8 +68,8 @@ __device__ inline void block_minmax(float lo[3], float hi[3], float (*sh)[6]) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        lo[c] = wave_min(lo[c]);
-        hi[c] = wave_max(hi[c]);
+        lo[c] = wave_minf(lo[c]);
+        hi[c] = wave_maxf(hi[c]);
     }
     if (lane == 0) {
 #pragma unroll
@@ -97,8 +82,8 @@ __device__ inline void block_minmax(float lo[3], float hi[3], float (*sh)[6]) {
     if (w == 0) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            lo[c] = wave_min(lane < nw ? sh[lane][c] : FLT_MAX);
-            hi[c] = wave_max(lane < nw ? sh[lane][3 + c] : -FLT_MAX);
+            lo[c] = wave_minf(lane < nw ? sh[lane][c] : FLT_MAX);
+            hi[c] = wave_maxf(lane < nw ? sh[lane][3 + c] : -FLT_MAX);
         }
     }
 }
@@ -211,23 +196,18 @@ struct MergeLayout {
 
 MergeLayout merge_layout(char *base, int64_t Ps) {
     MergeLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off = align_up(off + bytes, 256);
-        return p;
-    };
+    Carve c(base);
     const size_t n = (size_t)(Ps > 0 ? Ps : 1), nw = (n + 63) / 64;
-    L.mask = reinterpret_cast<unsigned long long *>(take(sizeof(unsigned long long) * nw));
-    L.cnt = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * nw));
-    L.pre = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * nw));
-    L.list = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * n));
+    L.mask = c.take<unsigned long long>(sizeof(unsigned long long) * nw);
+    L.cnt = c.take<uint32_t>(sizeof(uint32_t) * nw);
+    L.pre = c.take<uint32_t>(sizeof(uint32_t) * nw);
+    L.list = c.take<uint32_t>(sizeof(uint32_t) * n);
     size_t bytes = 0;
     (void)rocprim::exclusive_scan(nullptr, bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, nw,
                             rocprim::plus<uint32_t>());
     L.tmp_bytes = bytes;
-    L.tmp = take(bytes);
-    L.total = off;
+    L.tmp = c.take(bytes);
+    L.total = c.off;
     return L;
 }
 

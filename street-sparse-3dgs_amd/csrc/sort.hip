@@ -1,6 +1,7 @@
-// sort.hip -- rocPRIM pair sorts, key runs and scans (knn.hip, gtcloud.hip, lidar.hip).  The
-// rasterizer's depth sort is dsort.hip.  Kept in its own translation unit: rocPRIM's templates
-// dominate compile time.
+// sort.hip -- rocPRIM pair sorts, key runs and scans: knn.hip's Morton order, the cell table of the
+// sparse cell grid (grid_cell.h, built in cell_grid.hip for gtcloud.hip and lidar.hip), the voxel
+// mean, hier_build.hip and mesh_depth.hip.  The rasterizer's depth sort is dsort.hip.  Kept in its
+// own translation unit: rocPRIM's templates dominate compile time.
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include "gsr_launch.h"
@@ -28,7 +29,7 @@ hipError_t sort_pairs(void *tmp, size_t tmp_bytes, const uint32_t *kin, uint32_t
     return rocprim::radix_sort_pairs<OnesweepCfg>(tmp, tmp_bytes, kin, kout, vin, vout, n, 0, end_bit, s);
 }
 
-// 64-bit cell keys of the ground-truth cloud's grid (gtcloud.hip): once per cloud, default config
+// 64-bit keys (the cell keys of grid_cell.h's grids): once per index, default config
 size_t sort_pairs64_temp_bytes(size_t n, int end_bit) {
     size_t bytes = 0;
     rocprim::radix_sort_pairs(nullptr, bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr,

@@ -292,6 +292,39 @@ def mesh_case_d2(name):
     return d2
 
 
+# ---- one cell, one run: the query walk's own boundaries -----------------------------------------
+
+ONE_CELL_COUNTS = (16, 17, 64, 65)  # the lane's longest run, the wave's shortest, one slice, a slice and one
+ONE_CELL_NEAR = 0.03                # the distance of a point near at every queried distance
+_ONE_CELL_D = (ONE_CELL_NEAR, 0.5, 0.07, 0.15)  # by row % 4: near at every distance, at none, from 0.1, at 0.2
+
+
+@functools.lru_cache(maxsize=None)
+def one_cell_case(F):
+    """F triangles of 1 cm inside a cube of 0.19 m, below the cell edge of an index built for
+    MAX_DISTANCE (0.2 m): one cell, one run of F references in triangle order.  The first F - 1 sit in
+    the cube's low corner and the last one in the opposite corner 0.31 m away, so it alone is in reach of
+    the points, which lie beyond it on the diagonal: whoever finds a triangle has read the end of the
+    run.  "points" is (3, 65, 3), a second wave of one lane each: [0] distances by row % 4 as
+    _ONE_CELL_D (the 0.5 m ones have no vertex in reach on any axis and do not search); [1], [2] row 0 /
+    row 63 alone at ONE_CELL_NEAR and every other row 10 m away, so the wave's broadcast has its owner
+    at either end."""
+    rng = np.random.default_rng(300 + F)
+    c = np.concatenate([rng.uniform(0.0, 0.02, (F - 1, 1, 3)), np.full((1, 1, 3), 0.18)])
+    v, f = _mesh(c + rng.uniform(0.0, 0.01, (F, 3, 3)))
+    last = v[-3:].astype(np.float64)
+    tip = last[np.argmax(last.sum(1))]  # the last triangle's vertex farthest along the diagonal
+    u = _unit([1.0, 1.0, 1.0])
+    side = rng.uniform(-0.002, 0.002, (65, 3))
+    mixed = tip + u * np.array(_ONE_CELL_D)[np.arange(65) % 4, None] + side
+    sets = [mixed]
+    for lane in (0, 63):
+        p = tip + 10.0 + side
+        p[lane] = tip + u * ONE_CELL_NEAR + side[lane]
+        sets.append(p)
+    return _case(v, f, np.array(sets))
+
+
 # max_distance = 0.125 and a triangle with n = (0, 0, 1): the points at height 0.125 have d2 = T exactly
 TIE_CASE = _case(np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32), np.array([[0, 1, 2]], np.int32),
                  np.array([[0.25, 0.25, 0.125], [0.25, 0.5, -0.125], [-0.125, 0.5, 0.0], [1.125, 0.0, 0.0],

@@ -161,6 +161,60 @@ def test_one_crowded_cell():
     assert 0.2 < want[:1200].mean() < 0.95 and 0.2 < want[1200:2000].mean() < 0.8
 
 
+def one_cell_problem(G, thr=0.25):
+    """G points inside a cube of side thr / 2 (below the cell edge: one cell, one run of G points in
+    input order) and three sets of 65 queries, a second wave of one lane each.  Rows 1 .. G - 2 lie in
+    the cube's lowest layer, row 0 in its low corner's opposite XY corner at the bottom, the last row at
+    the top centre: it alone is within thr of a query 0.9 thr above it, so whoever finds a point has
+    read the end of the run.  [0]: by row % 4 such a query (rows 0 and 3 mod 4), one 3 thr above the
+    cube (no point in reach along z: no search) and one 0.95 thr below the corner (x_min, y_min) (it
+    walks the whole run and stays far).  [1] .. [4]: row 0 / row 63 alone inside the XY bounds, above the
+    last point or below the corner: the owner of the wave's run at either end of the wave."""
+    rng = np.random.default_rng(400 + G)
+    o, s = np.array([1.0, 2.0, 3.0]), thr / 2
+    cloud = o + rng.random((G, 3)) * [s, s, 0.05 * thr] + [0.0, 0.0, 0.1 * thr]
+    cloud[0] = o + [s, s, 0.0]
+    cloud[1] = o + [0.0, 0.0, 0.1 * thr]
+    cloud[G - 1] = o + [s / 2, s / 2, s]
+    above = o + np.concatenate([rng.random((65, 2)) * s, np.full((65, 1), s + 0.9 * thr)], 1)
+    high = above + [0.0, 0.0, 2.1 * thr]
+    below = np.tile(o + [0.0, 0.0, -0.95 * thr], (65, 1))
+    kind = np.arange(65) % 4
+    mixed = np.where((kind == 1)[:, None], high, np.where((kind == 2)[:, None], below, above))
+    sets = [mixed]
+    for lane in (0, 63):
+        for src in (above, below):
+            q = mixed + [-1.0, 0.0, 0.0]  # outside the XY bounds
+            q[lane] = src[lane]
+            sets.append(q)
+    return cloud.astype(np.float32), [q.astype(np.float32) for q in sets]
+
+
+@pytest.mark.parametrize("G", [16, 17, 64, 65, 129])
+def test_one_cell_run_lengths_and_the_owner_broadcast(G):
+    """One cell holding one run of G points, G on either side of the lane / wave split and of a
+    64-point slice, with the only point within thr at the run's end, so an early exit cannot hide a
+    slice that was not read; the wave's run owned by lane 0 and by lane 63."""
+    from gs_train.gtcloud import GtPointCloud
+    thr = 0.25
+    cloud, sets = one_cell_problem(G, thr)
+    c = GtPointCloud(cloud, threshold=thr, device=DEV)
+    try:
+        assert c.cells == 1 and c.G == G  # the run length is G
+        for k, q in enumerate(sets):
+            want = gt_ref.far_mask(q, cloud, thr)
+            inside = gt_ref.inside_bounds(q, cloud)
+            if k == 0:
+                assert inside.all() and np.array_equal(want, np.arange(65) % 4 % 3 != 0)  # both decisions
+            else:
+                lane = (0, 0, 63, 63)[k - 1]
+                assert np.array_equal(np.nonzero(inside)[0], [lane]) and want[lane] == (k % 2 == 0)
+            got = c.far_mask(torch.tensor(q, device=DEV)).cpu().numpy()
+            assert np.array_equal(got, want), (G, k, np.nonzero(got != want)[0])
+    finally:
+        c.close()
+
+
 def test_far_mask_with_existing_and_protected_masks():
     cloud, q = _random_problem(0.3, seed=3)
     rng = np.random.default_rng(4)

@@ -58,6 +58,29 @@ def test_near_mask_equals_the_float64_mask(name):
         index.close()
 
 
+@pytest.mark.parametrize("F", C.ONE_CELL_COUNTS)
+def test_one_cell_run_lengths_and_the_owner_broadcast(F):
+    """One cell holding one run of F references, F on either side of the lane / wave split and of a
+    64-reference slice, with the only triangle in reach at the run's end; the owner of the wave's run in
+    lane 0 and in lane 63, and a second wave of one lane (tests/lidar_cases.py one_cell_case)."""
+    from gs_train.lidar import MeshIndex
+    c = C.one_cell_case(F)
+    index = MeshIndex(c["vertices"], c["faces"], max_distance=C.MAX_DISTANCE, device=DEV)
+    try:
+        info = index.info()
+        assert info["cells"] == 1 and info["references"] == F
+        for k, pts in enumerate(c["points"]):
+            d2 = R.min_d2(pts, c["vertices"], c["faces"], np.float64)
+            for q in C.QUERY_DISTANCES:
+                want = R.near_mask(pts, d2, q)
+                assert want.any() and not want.all()  # the reference makes both decisions
+                got = index.near_mask(_t(pts), max_distance=q).cpu().numpy()
+                bad = np.nonzero(got != want)[0]
+                assert len(bad) == 0, (F, k, q, bad[:8], np.sqrt(d2[bad[:8]]))
+    finally:
+        index.close()
+
+
 def test_threshold_is_inclusive_on_an_exact_tie():
     """max_distance = 0.125 and points at exactly that distance from the face, an edge and a vertex of
     a triangle with power-of-two coordinates: every fp32 operation of the rule is exact, d2 = T."""

@@ -182,6 +182,30 @@ def test_cases_cover_what_they_claim():
                                           C.TIE_DISTANCE), C.TIE_EXPECTED)
 
 
+@pytest.mark.parametrize("F", C.ONE_CELL_COUNTS)
+def test_one_cell_cases_are_what_they_claim(F):
+    """The mesh fits under the cell edge of an index built for MAX_DISTANCE; in every point set and at
+    every queried distance the reference makes both decisions, the last triangle alone is in reach of
+    the near points, no distance is within GUARD of a threshold and the fp32 restatement agrees."""
+    c = C.one_cell_case(F)
+    v, f = c["vertices"], c["faces"]
+    assert len(f) == F and (v.max(0) - v.min(0)).max() < 2 * C.MAX_DISTANCE
+    assert c["points"].shape == (3, 65, 3)
+    for k, pts in enumerate(c["points"]):
+        d2 = R.min_d2(pts, v, f)
+        d_all = np.sqrt(d2)
+        d_last = np.sqrt(R.min_d2(pts, v, f[-1:]))
+        d_rest = np.sqrt(R.min_d2(pts, v, f[:-1]))
+        assert d_rest.min() > max(C.QUERY_DISTANCES) + C.GUARD and np.array_equal(d_all, d_last)
+        for q in C.QUERY_DISTANCES:
+            assert (np.abs(d_all - q) > C.GUARD).all()
+            want = R.near_mask(pts, d2, q)
+            assert want.any() and not want.all(), (F, k, q)
+            assert np.array_equal(R.near_mask_f32(pts, v, f, q), want)
+        near = d_all <= C.QUERY_DISTANCES[0]
+        assert np.array_equal(np.nonzero(near)[0], np.arange(0, 65, 4) if k == 0 else [(0, 63)[k - 1]])
+
+
 # ---- the C boundary ------------------------------------------------------------------------------
 
 def _declared():
