@@ -257,6 +257,15 @@ VIEWS_SIGNATURES = {
     "gsr_view_expand": (_i, [_i, _i, _vp, _vp, _i, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/gsr_depth_scale.h (the per-image scale / offset of depth maps of unknown scale).
+# New entry points only: the ABI version stays
+DEPTH_SCALE_SIGNATURES = {
+    "gsr_depth_scale_lds_capacity": (_i, []),
+    "gsr_depth_scale_scratch_bytes": (ctypes.c_size_t, [_i64]),
+    "gsr_depth_scale_fit": (_i, [_i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i, _i, _vp, _i,
+                                 _vp, _vp, _vp]),
+}
+
 ABI_VERSION = 7
 _lib = None
 
@@ -282,7 +291,8 @@ def load(path: str = LIB_PATH):
                               + list(HIER_BUILD_SIGNATURES.items()) + list(HIER_MERGE_SIGNATURES.items())
                               + list(LPIPS_SIGNATURES.items()) + list(MODEL_INIT_SIGNATURES.items())
                               + list(LIDAR_SIGNATURES.items()) + list(MESH_DEPTH_SIGNATURES.items())
-                              + list(CHUNKER_SIGNATURES.items()) + list(VIEWS_SIGNATURES.items())):
+                              + list(CHUNKER_SIGNATURES.items()) + list(VIEWS_SIGNATURES.items())
+                              + list(DEPTH_SCALE_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
