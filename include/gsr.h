@@ -215,8 +215,14 @@ int gsr_segment_layout_check(int64_t K, int L, int Lf, int64_t *need, int64_t *h
 /* Depth-order strategy of the binning, process-wide.  0: the local sort -- level 1 in Gaussian
  * index order, each superblock list sorted by depth in LDS -- except for frames forwarded in
  * deterministic mode and frames with a superblock list longer than the LDS sort holds, which take
- * the global sort.  1 (default): always the global depth sort of all P Gaussians (dsort.hip).  Both
- * give the same per-tile lists.  Returns the previous mode (or GSR_ERR_INVALID_ARGUMENT). */
+ * the global sort.  1: always the global depth sort of all P Gaussians (dsort.hip).  2 (default):
+ * chosen per frame -- the local sort when the frame is not forwarded in deterministic mode, its
+ * superblock grid fits one round of the LDS sort's workgroups (two per compute unit: a 1080p frame's
+ * 510 superblocks on 256 units, not a 1536 x 1536 frame's 576) and the longest superblock list of the
+ * calling thread's recent frames on the device fits the LDS sort; after a frame with a longer list the
+ * next 256 frames take the global sort without trying the local one (gsr_reset_capacity_hint forgets
+ * that history too).  All give the same per-tile lists.  Returns the previous mode (or
+ * GSR_ERR_INVALID_ARGUMENT; modes 0 to 2). */
 int gsr_set_binning(int mode);
 
 /* Forward statistics since load: out[0] = frames rasterized (P > 0), out[1] = frames whose
@@ -241,8 +247,9 @@ int gsr_forward_stats(int64_t *out, int n);
 int gsr_fwd_pool_stats(int64_t *out, int n, int reset);
 
 /* Forget the calling thread's point-list capacity hint (the largest K of its last 256 frames per
- * device) and its split-gate history: the next frame reads K before binning, as the first one does,
- * and the gated splits wait for a long-list frame again.  For a caller that switches to a much
+ * device) and its split-gate and list-gate history: the next frame reads K before binning, as the
+ * first one does, the gated splits wait for a long-list frame again, and binning mode 2 tries the
+ * local sort again.  For a caller that switches to a much
  * smaller workload (the buffers follow the hint) and for tests.  ABI 3. */
 int gsr_reset_capacity_hint(void);
 

@@ -26,8 +26,8 @@
 // laid out SB-major instead of row-major; every consumer goes through `ranges`, so the layout of
 // whole tiles in point_list is free.  Traffic ~ 8 B per SB instance + 4 B per tile instance written.
 //
-// Two ways to reach depth order (gsr_set_binning; rasterizer.hip, DESIGN.md 7.4):
-//   global sort (default) dsort.hip's depth order of all P Gaussians, level 1 over it, and
+// Two ways to reach depth order (gsr_set_binning; rasterizer.hip, DESIGN.md 7.4 and 29):
+//   global sort (mode 1)  dsort.hip's depth order of all P Gaussians, level 1 over it, and
 //                         tile_bin over the (already depth-ordered) SB lists.  Also what a
 //                         local-sort frame falls back to when an SB list is longer than the LDS
 //                         sort holds (kSortCap), and what deterministic mode uses (its backward
@@ -37,6 +37,10 @@
 //                         the raw depth bits of gs.dkey inside LDS (stable LSD radix over the list's
 //                         own key range: equal depths keep id order) and bins it into the SB's tiles
 //                         from LDS.  The column scan publishes K and the longest SB list.
+//   auto (mode 2, the     per frame, on the host: the local sort where the SB grid fits one round
+//   default)              of sb_sort_bin workgroups (sort_blocks_per_cu) and the recent frames'
+//                         longest SB list (the column scan stores it to a pinned word on either
+//                         path) fits the LDS sort; else the global sort, with no local attempt.
 #include "gsr_launch.h"
 
 namespace gsr {
@@ -235,6 +239,17 @@ constexpr int kSBWaves = kSBThreads / 64;
 constexpr int kSortCap = GSR_SORT_CAP;            // longest SB list the local sort holds in LDS
 constexpr int kSBItems = kSortCap / kSBThreads;   // keys per thread
 static_assert(kSortCap % kSBThreads == 0 && kSortCap <= 65536, "kSortCap: a multiple of 1024, 16-bit positions");
+// sb_colscan publishes one longest-list word for both paths (kHostSBList): a list the local sort
+// holds must never arm the tile binning's split
+static_assert(GSR_TB_SPLIT == 0 || kSortCap <= GSR_TB_SPLIT, "the split gate reads local frames' list lengths too");
+// sb_sort_bin's residency: its registers are budgeted for kSBWavesPerSIMD waves per SIMD (launch
+// bounds), its LDS is the key / position buffer, the per-wave digit counters, their sums and the range
+constexpr int kSBWavesPerSIMD = 8;
+constexpr size_t kSBSortLds = kSortCap * (sizeof(uint32_t) + sizeof(uint16_t)) +
+                              (kSBWaves + 1) * 256 * sizeof(uint32_t) + 2 * sizeof(uint32_t);
+constexpr int kSIMDsPerCU = 4, kLdsPerCU = 160 * 1024;  // CDNA4
+constexpr int kSBSortPerCU = std::min<int>(kSBWavesPerSIMD * kSIMDsPerCU / kSBWaves, (int)(kLdsPerCU / kSBSortLds));
+static_assert(kSBSortPerCU >= 1, "sb_sort_bin does not fit a CU");
 
 // Level 1, pass 2: per SB, exclusive scan of the Gaussian counts over chunks (in place) and the
 // SB totals of Gaussians and instances; the last workgroup to finish (a per-frame counter in the
@@ -336,6 +351,7 @@ __global__ __launch_bounds__(kColThreads) void sb_colscan_kernel(SBGrid sg, uint
             // through the global sort, which stores the real K there again)
             *fw.dev_K = mg > (uint32_t)kSortCap ? 0xFFFFFFFFu : ci;
             *fw.dev_maxsb = mg;
+            if (fw.dev_tb_items) *fw.dev_tb_items = 0u;
             if (fw.host) {
                 __hip_atomic_store(&fw.host[kHostMaxSB], mg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 __hip_atomic_store(&fw.host[kHostP1], cg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -870,7 +886,7 @@ __device__ __forceinline__ void sbs_walk(int shift, const uint32_t *ids, const u
 // __launch_bounds__(1024, 8): registers budgeted for 8 waves per SIMD -- two 1024-thread
 // workgroups per CU (66 KiB of LDS each); at the compiler's default (7 waves per SIMD, 104 SGPRs)
 // only one fit and the 510 superblocks of a 1080p frame ran in two rounds
-__global__ __launch_bounds__(kSBThreads, 8) void sb_sort_bin_kernel(SBGrid sg, int gx, int gy,
+__global__ __launch_bounds__(kSBThreads, kSBWavesPerSIMD) void sb_sort_bin_kernel(SBGrid sg, int gx, int gy,
                                                                 const uint32_t *__restrict__ base_g,
                                                                 const uint32_t *__restrict__ base_i,
                                                                 const uint4 *__restrict__ sblist,
@@ -888,6 +904,8 @@ __global__ __launch_bounds__(kSBThreads, 8) void sb_sort_bin_kernel(SBGrid sg, i
     __shared__ uint32_t s_wh[kSBWaves][256];  // per-wave digit counts; later the per-wave tile counters
     __shared__ uint32_t s_bex[256];
     __shared__ uint32_t s_lo, s_hi;
+    static_assert(sizeof(s_key) + sizeof(s_pos) + sizeof(s_wh) + sizeof(s_bex) + 2 * sizeof(uint32_t) == kSBSortLds,
+                  "kSBSortLds (sort_blocks_per_cu) is this kernel's LDS");
     const int s = blockIdx.x;
     const int t = threadIdx.x, w = t >> 6, lane = t & 63;
     const int side = 1 << sg.shift, tps = side * side;
@@ -1069,6 +1087,7 @@ __global__ __launch_bounds__(kSBThreads, 8) void sb_sort_bin_kernel(SBGrid sg, i
 }  // namespace
 
 int sort_cap() { return kSortCap; }
+int sort_blocks_per_cu() { return kSBSortPerCU; }
 
 int debug_trace(int64_t *out, int n, int reset) {
     static unsigned long long v[2048 * 8];

@@ -699,8 +699,9 @@ __host__ __device__ __forceinline__ const uint32_t *drect4_of(const GeomState &g
 // Frame words a local-sort frame's column scan publishes (binning.hip): device copies for the
 // kernels (dev_K = the depth sort's K word, which every capacity test reads) and, when host is set,
 // the pinned host words the host waits on.  host[kHostK] is stored last.
-// kHostSBList / kHostTileList: every frame's longest superblock list (sb_colscan) and longest tile
-// list (the forward's tile_order), read by the host as the split gate's hint (rasterizer.hip)
+// kHostSBList / kHostTileList: every frame's longest superblock list (sb_colscan, on either path)
+// and longest tile list (the forward's tile_order), read by the host as the split gate's and the
+// list gate's hint (rasterizer.hip)
 // Sticky flags the kernels set with plain system-scope stores (read-modify-write atomics on pinned host
 // memory need PCIe atomics, which a host may not have) and the host's next call takes:
 // kHostErr: a depth-sort lookback spin gave up; kHostFwdErr: a forward worker's wait for a
@@ -724,6 +725,9 @@ struct FrameWords {
     uint32_t *dev_K;      // nullptr: global-sort frame (dsort publishes K)
     uint32_t *dev_maxsb;  // longest SB list
     uint32_t *host;       // pinned host words (HostWord indices) or nullptr
+    // the tile binning's slice count (tb_flag[nsb], which gsr_frame_stats reads): a local frame
+    // queues no slices and stores 0 there -- one store, the per-superblock flags stay untouched
+    uint32_t *dev_tb_items = nullptr;
 };
 
 struct BinningState {       // per tile instance

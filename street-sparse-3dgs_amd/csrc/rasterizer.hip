@@ -31,12 +31,13 @@ int fail(int code, const std::string &msg) {
 }
 // forward statistics (gsr_forward_stats): frames, binning re-runs at K (capacity hint short)
 std::atomic<int64_t> g_frames{0}, g_reruns{0}, g_local_frames{0}, g_fallbacks{0};
-// binning mode (gsr_set_binning): 0 = local sort where it applies, 1 = always the global depth sort.
-// Default 1: on the 1M-Gaussian 1080p bench frame the local path measured 2801 Mpix/s against
-// 2909 (its level-1 kernels and the LDS sort share the chip with the SH colour pass, which the
-// global sort leaves half of the CUs to)
+// binning mode (gsr_set_binning): 0 = local sort where it applies, 1 = always the global depth sort,
+// 2 = chosen per frame (auto_local below).
+// Default 2: the local path is 7 front-end launches against 12 and wins on frames whose superblock
+// grid fits one round of sb_sort_bin workgroups and whose lists fit its LDS; every other frame is
+// sent straight to the global sort
 #ifndef GSR_BINNING_DEFAULT
-#define GSR_BINNING_DEFAULT 1
+#define GSR_BINNING_DEFAULT 2
 #endif
 std::atomic<int> g_binning_mode{GSR_BINNING_DEFAULT};
 std::atomic<int> g_live_list{0};  // gsr_set_live_list
@@ -170,6 +171,28 @@ struct ThreadDevice {
     // whose longest tile / superblock list called for them -- the kernels report those lengths in
     // the pinned words, read at the next forward.
     int64_t frame_no = 0, long_tile_at = 0, long_sb_at = 0;
+    // The list gate (binning mode 2): the frame whose longest superblock list was last seen above
+    // list_gate_len() -- the kSplitMemory frames after it go straight to the global sort instead of
+    // trying the local sort and re-running level 1.  No history (a thread's first frame, after
+    // gsr_reset_capacity_hint): the frame tries the local sort.
+    int64_t long_list_at = -2 * kSplitMemory;
+
+    // the longest list the gate still calls short: 7/8 of what the LDS sort holds (the longest
+    // list of a training loop's views moves by a few per cent from view to view)
+    static uint32_t list_gate_len() { return (uint32_t)sort_cap() - (uint32_t)sort_cap() / 8u; }
+    // The longest superblock list of the frames before, as the pinned word holds it now (sb_colscan
+    // stores every frame's there, on either path; 0: no frame yet).  A frame reads it once, before
+    // its first binning launch, for both gates: a local frame's own column scan stores it before a
+    // fallback reaches split_gate, and the frames before must decide the splits of that re-run as
+    // they do on a frame sent to the global sort directly.
+    uint32_t recent_sb_list() const { return pinned ? __atomic_load_n(&pinned[kHostSBList], __ATOMIC_RELAXED) : 0u; }
+    // Do the recent frames' lists fit the local sort (sb_list: recent_sb_list())?  Global frames keep
+    // the gate shut while their lists stay long: the kSplitMemory frames after the last long one.
+    bool list_gate(uint32_t sb_list) {
+        const int64_t f = frame_no + 1;  // this frame's number (split_gate counts it)
+        if (sb_list > list_gate_len()) long_list_at = f - 1;  // the frame before, at the latest
+        return f - long_list_at > kSplitMemory;
+    }
 
     int ensure() {
         if (!pinned) {
@@ -186,10 +209,10 @@ struct ThreadDevice {
     }
     // the gate on this frame's requested splits: the longest lists of the frames before (whatever
     // the pinned words hold now) arm them
-    void split_gate(uint32_t fseg_min, uint32_t *fseg_req, uint32_t *tb_req) {
+    // (sl: recent_sb_list() as read before the frame's first binning launch)
+    void split_gate(uint32_t fseg_min, uint32_t *fseg_req, uint32_t *tb_req, uint32_t sl) {
         const int64_t f = ++frame_no;
         const uint32_t tl = __atomic_load_n(&pinned[kHostTileList], __ATOMIC_RELAXED);
-        const uint32_t sl = __atomic_load_n(&pinned[kHostSBList], __ATOMIC_RELAXED);
         if (*fseg_req && tl > fseg_min) long_tile_at = f;
         if (*tb_req && sl > *tb_req) long_sb_at = f;
         if (g_split_gate.load(std::memory_order_relaxed)) {
@@ -207,7 +230,7 @@ struct ThreadDevice {
     }
     void reset() {  // gsr_reset_capacity_hint
         if (pinned) pinned[kHostTileList] = pinned[kHostSBList] = 0u;
-        long_tile_at = long_sb_at = frame_no - 2 * kSplitMemory;
+        long_tile_at = long_sb_at = long_list_at = frame_no - 2 * kSplitMemory;
         khint = 0;
         khead = 0;
         for (int i = 0; i < kKHist; i++) khist[i] = 0;
@@ -633,6 +656,20 @@ ColorPlan color_plan(int P, bool local, bool split, Device *dev) {
     return {dsort_blocks(P) >= 2 * dev->cus, 0};
 }
 
+// Binning mode 2: the local sort for a frame of nsb superblocks?  It saves the global sort's five
+// launches, and pays them back with interest where
+//   - sb_sort_bin's grid (one workgroup per superblock) needs a second round: more superblocks
+//     than its workgroups resident on the chip (two per CU: 512 on 256 CUs against the 510
+//     superblocks of 1080p; a 1536 x 1536 street frame has 576), or
+//   - a list is longer than the LDS sort holds, and the frame runs level 1 twice: the list gate
+//     (ThreadDevice::list_gate) keeps such frames off the local path from the second one on.
+// Both are known before the frame's first binning launch.  The gate is consulted on every frame,
+// so its history is that of all recent frames, whatever their path.
+bool auto_local(int nsb, const Device *dev, ThreadDevice *td, uint32_t recent_sb_list) {
+    const bool recent_fit = td->list_gate(recent_sb_list);
+    return recent_fit && nsb <= sort_blocks_per_cu() * dev->cus.load(std::memory_order_relaxed);
+}
+
 // One forward call: what its stages share.
 struct Frame {
     hipStream_t s;  // of the call's arguments
@@ -918,8 +955,12 @@ int gsr::ForwardCall::run(gsr_resize_fn geom_buffer, gsr_resize_fn binning_buffe
     // Depth order (binning.hip): the local sort (level 1 in index order, each superblock list sorted
     // in LDS) unless the frame is in deterministic mode (its backward needs the global sort's
     // record offsets) or the global sort is forced; a local frame whose longest SB list exceeds
-    // what the LDS sort holds is re-run through the global sort.
-    bool &local = f.local = P > 0 && g_binning_mode.load(std::memory_order_relaxed) == 0 && !det_fwd;
+    // what the LDS sort holds is re-run through the global sort.  Mode 2 takes the local sort only
+    // where it wins and is not expected to fall back (auto_local).
+    const int bmode = g_binning_mode.load(std::memory_order_relaxed);
+    const uint32_t sb_seen = dev ? thread_device(dev).recent_sb_list() : 0u;  // for the list gate and the split gate
+    const bool fits = P > 0 && dev && auto_local(gs.sb.nsb, dev, &thread_device(dev), sb_seen);  // (keeps the gate's history in every mode)
+    bool &local = f.local = P > 0 && !det_fwd && (bmode == 0 || (bmode == 2 && fits));
     const ColorPlan color = color_plan(P, local, split, dev);
     f.color_blocks = color.blocks;
     // A fused hierarchy cut whose colour pass forks early (config 5): forked before the preprocess,
@@ -953,8 +994,10 @@ int gsr::ForwardCall::run(gsr_resize_fn geom_buffer, gsr_resize_fn binning_buffe
     }
     if (local) {
         {
-            StageTimer st(1, s);  // level-1 counts, SB bases, K
-            launch_binning_count(P, cam, gs, true, FrameWords{dsort_K_word(gs), dsort_maxsb_word(gs), td.pinned_dev}, s);
+            StageTimer st(1, s);  // level-1 counts, SB bases, K; the longest list also for the gates
+            launch_binning_count(P, cam, gs, true,
+                                 FrameWords{dsort_K_word(gs), dsort_maxsb_word(gs), td.pinned_dev, gs.tb_flag + gs.sb.nsb},
+                                 s, 0u, td.pinned_dev + kHostSBList);
             if (f.k_ready) (void)hipEventRecord(f.k_ready, s);
         }
         if ((rc = check("binning (counts)", debug, s))) return rc;
@@ -979,7 +1022,7 @@ int gsr::ForwardCall::run(gsr_resize_fn geom_buffer, gsr_resize_fn binning_buffe
     // and the gate must agree even if gsr_set_fwd_split_min runs meanwhile
     f.fseg_min = f.fseg_req ? fseg_min_len(f.fseg_req) : 0u;
     f.spin = fwd_spin(td.pinned_dev);
-    if (P > 0) td.split_gate(f.fseg_min, &f.fseg_req, &f.tb_req);
+    if (P > 0) td.split_gate(f.fseg_min, &f.fseg_req, &f.tb_req, sb_seen);
     const int64_t cap0 = defer ? td.khint : f.K;
     if ((rc = f.bin_and_render(cap0, false))) return rc;
     if (!f.have_K && (rc = f.read_K())) return rc;
@@ -1283,7 +1326,7 @@ int gsr_set_bwd_segment(int L) {
 }
 
 int gsr_set_binning(int mode) {
-    if (mode < 0 || mode > 1) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_set_binning: mode 0 or 1");
+    if (mode < 0 || mode > 2) return fail(GSR_ERR_INVALID_ARGUMENT, "gsr_set_binning: mode 0, 1 or 2");
     return g_binning_mode.exchange(mode);
 }
 

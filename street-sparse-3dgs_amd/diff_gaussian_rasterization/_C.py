@@ -91,7 +91,9 @@ def set_deterministic(enable: bool) -> bool:
 
 def set_binning(mode: int) -> int:
     """Depth-order strategy (gsr_set_binning): 0 = local per-superblock sort where it applies,
-    1 = always the global depth sort (default).  Process-wide; returns the previous mode."""
+    1 = always the global depth sort, 2 (default) = per frame: the local sort where the superblock
+    grid fits one round of its workgroups and the recent frames' longest superblock list fits its
+    LDS, else the global sort.  Same lists either way.  Process-wide; returns the previous mode."""
     r = _L.gsr_set_binning(int(mode))
     _check(0 if r >= 0 else r, "set_binning")
     return r
