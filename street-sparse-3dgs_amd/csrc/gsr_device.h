@@ -68,6 +68,10 @@ __device__ __forceinline__ float4 xf_point44(float3 p, const Mat4 &M) {
                        m[3] * p.x + m[7] * p.y + m[11] * p.z + m[15]);
 }
 
+// in_frustum's near test on the view-space mean (prefiltered is treated as a plain cull): the
+// preprocess's cull and station.hip's per-face keep test are this one expression
+__device__ __forceinline__ bool view_depth_culled(float3 pv) { return pv.z <= 0.2f; }
+
 // upstream evaluates ((v + 1.0) * S - 1.0) * 0.5 in double
 __device__ __forceinline__ float ndc2pix(float v, int S) {
     return (float)((((double)v + 1.0) * (double)S - 1.0) * 0.5);

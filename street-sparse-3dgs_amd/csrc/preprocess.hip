@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
                                          cut_lerp(ct, means3D[3 * ci + 2], means3D[3 * pi + 2]))
                            : make_float3(ldp(means3D + 3 * i), ldp(means3D + 3 * i + 1), ldp(means3D + 3 * i + 2));
     const float3 pv = xf_point43(p, V);
-    if (pv.z <= 0.2f) return;  // in_frustum (prefiltered is treated as a plain cull)
+    if (view_depth_culled(pv)) return;  // in_frustum (prefiltered is treated as a plain cull)
     const float4 ph = xf_point44(p, Pm);
     const float pw = 1.0f / (ph.w + 0.0000001f);
     const float ndcx = ph.x * pw, ndcy = ph.y * pw;

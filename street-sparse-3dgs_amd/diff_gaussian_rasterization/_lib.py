@@ -266,6 +266,21 @@ DEPTH_SCALE_SIGNATURES = {
                                  _vp, _vp, _vp]),
 }
 
+# include/gsr_station.h (the faces of one recording position from one hierarchy cut).
+# New entry points only: the ABI version stays
+STATION_MAX_FACES = 8
+STATION_FACE_ARRAYS = 6
+_szp = ctypes.POINTER(ctypes.c_size_t)
+STATION_SIGNATURES = {
+    "gsr_station_rows_scratch_bytes": (ctypes.c_size_t, [_i64, _i]),
+    "gsr_station_rows_layout": (ctypes.c_size_t, [_i, _i64p, _szp]),
+    "gsr_rasterize_station_forward": (_i, [RESIZE_FN, RESIZE_FN, RESIZE_FN, RESIZE_FN, _vp, _vp, ctypes.c_size_t,
+                                           _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp,
+                                           _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _i64p, _i64p, _i, _vp]),
+    "gsr_station_set_profiling": (_i, [_i]),
+    "gsr_station_stage_times_ms": (_i, [ctypes.POINTER(_f), _i]),
+}
+
 ABI_VERSION = 7
 _lib = None
 
@@ -292,7 +307,7 @@ def load(path: str = LIB_PATH):
                               + list(LPIPS_SIGNATURES.items()) + list(MODEL_INIT_SIGNATURES.items())
                               + list(LIDAR_SIGNATURES.items()) + list(MESH_DEPTH_SIGNATURES.items())
                               + list(CHUNKER_SIGNATURES.items()) + list(VIEWS_SIGNATURES.items())
-                              + list(DEPTH_SCALE_SIGNATURES.items())):
+                              + list(DEPTH_SCALE_SIGNATURES.items()) + list(STATION_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -11,6 +11,7 @@
   native_step.NativeTrainStep      the same iteration as one native call (gsr_train_step)
   synthetic                        seeded synthetic scenes / cameras
   evaluate.Evaluator               test-set PSNR / SSIM / iMAE / iRMSE, whole-image and per region (csrc/eval.hip)
+  station.StationRenderer          a recording position's cube faces from one hierarchy cut (csrc/station.hip)
   lpips.LpipsModel                 its LPIPS column: one VGG16 pass per frame, fused per-region taps (csrc/lpips.hip)
   hier_build.build_hierarchy       a trained chunk's LOD hierarchy (GaussianHierarchyCreator's step; csrc/hier_build.hip)
   hier_merge.merge_hierarchies     the chunks' hierarchies into the scene's (GaussianHierarchyMerger's step; csrc/hier_merge.hip)

@@ -130,7 +130,7 @@ def _morton3(q):
 
 
 def synthetic_lod_hierarchy(L, W, H, device, seed=0, branching=4, skybox=0, sh_degree=3, fovx_deg=60.0, zmin=2.0,
-                            zmax=40.0, log_scale_mean=-4.5, log_scale_std=0.5):
+                            zmax=40.0, log_scale_mean=-4.5, log_scale_std=0.5, layout="frustum"):
     """Config-5 stand-in with a real tree: L leaf Gaussians in the
     frustum, grouped bottom-up in Morton order, `branching` consecutive nodes per parent, up to one
     root.  Every node holds one Gaussian (leaf: count_leafs = 1; interior: count_merged = 1, the
@@ -140,14 +140,23 @@ def synthetic_lod_hierarchy(L, W, H, device, seed=0, branching=4, skybox=0, sh_d
     count_leafs, count_merged, start_children, count_children}, boxes (N, 2, 4) float32
     {minn.xyz, size | maxx.xyz, 0} with size = the box's largest extent -- the gaussianhierarchy
     layout (scene/gaussian_model.py:345, 424-425).  Gaussian attributes are *activated*, as
-    render_post reads them.  Works on any torch device."""
+    render_post reads them.  Works on any torch device.
+    layout="shell" (a station's surroundings, gs_train.station): the leaves fill the spherical shell
+    [zmin, zmax] around the origin in all directions and the skybox rows cover the whole sphere;
+    "frustum" (the default) is the layout above, value for value."""
     import torch
+    if layout not in ("frustum", "shell"):
+        raise ValueError(f"synthetic_lod_hierarchy: layout must be 'frustum' or 'shell', got {layout!r}")
     dev = torch.device(device)
     g = torch.Generator(device=dev).manual_seed(seed)
     view, proj, campos, tx, ty = camera(W, H, fovx_deg)
     u = lambda *s: torch.rand(*s, generator=g, device=dev)
     z = zmin + (zmax - zmin) * u(L)
-    means = torch.stack([(u(L) * 1.9 - 0.95) * tx * z, (u(L) * 1.9 - 0.95) * ty * z, z], 1)
+    if layout == "shell":
+        d = torch.randn(L, 3, generator=g, device=dev)
+        means = z[:, None] * d / d.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    else:
+        means = torch.stack([(u(L) * 1.9 - 0.95) * tx * z, (u(L) * 1.9 - 0.95) * ty * z, z], 1)
     scales = torch.exp(log_scale_mean + log_scale_std * torch.randn(L, 3, generator=g, device=dev))
     q = torch.randn(L, 4, generator=g, device=dev)
     rots = q / q.norm(dim=1, keepdim=True)
@@ -212,7 +221,8 @@ def synthetic_lod_hierarchy(L, W, H, device, seed=0, branching=4, skybox=0, sh_d
     if skybox:
         r = 200.0
         d = torch.randn(skybox, 3, generator=g, device=dev)
-        d[:, 2] = d[:, 2].abs() + 0.5
+        if layout != "shell":
+            d[:, 2] = d[:, 2].abs() + 0.5
         d = d / d.norm(dim=1, keepdim=True)
         sk = dict(means3D=r * d, scales=torch.full((skybox, 3), 2.0, device=dev),
                   rotations=torch.tensor([[1.0, 0, 0, 0]], device=dev).expand(skybox, 4),
@@ -222,6 +232,35 @@ def synthetic_lod_hierarchy(L, W, H, device, seed=0, branching=4, skybox=0, sh_d
     out.update(nodes=nodes, boxes=boxes, skybox=skybox, view=view, proj=proj, campos=campos, tanfovx=tx, tanfovy=ty,
                W=W, H=H, sh_degree=sh_degree, levels=len(levels))
     return out
+
+
+def cube_face_cameras(W, n_faces=6, center=(0.0, 0.0, 0.0), rig=None, znear=0.01, zfar=100.0):
+    """The W x W faces of a station at `center` with tanfov = 1 (90 degrees), as dicts with view, proj,
+    campos, tanfovx, tanfovy, W, H: n_faces = 4 looks along +z, +x, -z, -x (a turn about the y axis
+    each), 6 adds the two faces along the y axis.  Every face's campos is `center` as float32, bit for
+    bit (the view matrices carry -R center rounded to float32).  rig: an optional 3 x 3 world-to-rig
+    rotation applied before the faces' own."""
+    if n_faces not in (4, 6):
+        raise ValueError("cube_face_cameras: 4 horizontal faces or 6")
+    c = np.asarray(center, np.float32).reshape(3)
+    rig = np.eye(3) if rig is None else np.asarray(rig, np.float64).reshape(3, 3)
+    ry = lambda a: np.array([[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]])
+    rx = lambda a: np.array([[1, 0, 0], [0, math.cos(a), -math.sin(a)], [0, math.sin(a), math.cos(a)]])
+    turns = [ry(-k * math.pi / 2) for k in range(4)]
+    if n_faces == 6:
+        turns += [rx(math.pi / 2), rx(-math.pi / 2)]
+    Pm = projection_matrix(znear, zfar, math.pi / 2, math.pi / 2)
+    cams = []
+    for T in turns:
+        Rw2c = T @ rig
+        Rt = np.zeros((4, 4))
+        Rt[:3, :3] = Rw2c
+        Rt[:3, 3] = -Rw2c @ c.astype(np.float64)
+        Rt[3, 3] = 1.0
+        view = Rt.astype(np.float32).T.copy()
+        proj = (view @ Pm.T.astype(np.float32)).astype(np.float32)
+        cams.append(dict(view=view, proj=proj, campos=c.copy(), tanfovx=1.0, tanfovy=1.0, W=int(W), H=int(W)))
+    return cams
 
 
 def tau_threshold(tau, tanfovx, W):
