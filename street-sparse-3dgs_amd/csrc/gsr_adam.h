@@ -21,4 +21,43 @@ __device__ __forceinline__ void adam_at_g(const gsr_adam_group &G, int64_t e, fl
     G.param[e] = G.param[e] + (-G.step_size) * (m / denom);
 }
 
+// The dense step's flat runs (optim.hip dense_adam_flat_kernel) and the arithmetic of one element of
+// a run; post_step.hip's row-state kernel applies the same function, so the two cannot drift apart.
+constexpr int kMaxGroups = 8;
+constexpr int kAdamThreads = 256;
+
+struct FlatAdamRun {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    int64_t n;         // floats
+    int row;           // floats per row (the column of element e is e % row)
+    int split_col;     // columns < split_col take step0, the rest step1 (row: one step size)
+    float step0, step1;
+    float bc2s;
+    int vec;           // all four arrays 16-B aligned and row % 4 == 0: float4 access
+};
+struct FlatAdamArgs {
+    FlatAdamRun r[kMaxGroups];
+    int64_t block_start[kMaxGroups + 1];
+    int n;
+};
+constexpr int kFlatPerThread = 8;  // two float4 per lane
+constexpr int64_t kFlatPerBlock = (int64_t)kAdamThreads * kFlatPerThread;
+
+__device__ __forceinline__ void flat_adam_one(const FlatAdamRun &R, float &p, float &m, float &v, float g, float ss,
+                                              float b1, float b2, float omb1, float omb2, float eps) {
+    const float mm = m * b1 + omb1 * g;
+    const float vv = v * b2 + omb2 * (g * g);
+    const float denom = sqrtf(vv) / R.bc2s + eps;
+    m = mm;
+    v = vv;
+    p = p + (-ss) * (mm / denom);
+}
+
+// optim.hip: the flat runs of a dense step over `groups` (a column-split pair of one buffer merged
+// into one run); a group that is no whole-row run goes to rest[].  Returns the number of runs.
+int flat_adam_runs(int n_groups, const gsr_adam_group *groups, int64_t P, FlatAdamArgs &fa, int *rest, int &n_rest);
+
 }  // namespace gsr

@@ -7,6 +7,7 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_hier.h"
+#include "../../include/gsr_post.h"
 #include "gsr_launch.h"
 
 namespace gsr {
@@ -327,6 +328,20 @@ __global__ __launch_bounds__(256) void cut_bwd_sh_kernel(int64_t N, int64_t R, i
     if (cur >= 0) add4(dsh + 48 * cur + 4 * col, acc);
 }
 
+// The rows cut_bwd_kernel / cut_bwd_sh_kernel write or accumulate into, stamped with `value`
+// (gsr_cut_mark_rows, include/gsr_post.h): every cut row's child and (for a blended row) its parent,
+// and the S skybox rows -- cut_row's own c and p, so the backward and its mark cannot disagree.
+// Rows shared by several cut rows get the same value from each (plain stores).
+__global__ __launch_bounds__(256) void cut_mark_kernel(int64_t N, int64_t R, int64_t S, const int *__restrict__ ri,
+                                                       const int *__restrict__ pi, const float *__restrict__ w,
+                                                       int *__restrict__ stamp, int value) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R + S) return;
+    const CutRow q = cut_row(r, N, R, S, ri, pi, w);
+    if (q.c >= 0 && q.c < N) stamp[q.c] = value;
+    if (!q.copy && q.p >= 0 && q.p < N) stamp[q.p] = value;
+}
+
 }  // namespace
 }  // namespace gsr
 
@@ -500,6 +515,21 @@ int gsr_zero_grad_rows(int n, float *const *grads, const int64_t *widths, int64_
     hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)n), dim3(256), 0,
                        static_cast<hipStream_t>(stream), z, n, N, tail, rows, n_rows);
     return launched("gsr_zero_grad_rows");
+}
+
+int gsr_cut_mark_rows(int64_t N, int64_t R, int64_t S, const int *render_indices, const int *parent_indices,
+                      const float *interpolation_weights, int *stamp, int value, void *stream) {
+    if (N < 0 || R < 0 || S < 0 || S > N ||
+        (R > 0 && (!render_indices || !parent_indices || !interpolation_weights)) ||
+        (R + S > 0 && !stamp)) {
+        set_last_error("gsr_cut_mark_rows: bad sizes or NULL pointer (need 0 <= S <= N)");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (R + S == 0) return GSR_OK;
+    hipLaunchKernelGGL(cut_mark_kernel, dim3((unsigned)((R + S + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), N, R, S, render_indices, parent_indices,
+                       interpolation_weights, stamp, value);
+    return launched("gsr_cut_mark_rows");
 }
 
 }  // extern "C"

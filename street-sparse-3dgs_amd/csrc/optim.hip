@@ -16,6 +16,7 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_train.h"
+#include "gsr_adam.h"
 #include "gsr_launch.h"
 
 namespace gsr {
@@ -24,8 +25,6 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // Sparse Adam.
 
-constexpr int kMaxGroups = 8;
-constexpr int kAdamThreads = 256;
 
 struct AdamArgs {
     gsr_adam_group g[kMaxGroups];
@@ -225,36 +224,8 @@ __global__ __launch_bounds__(kAdamThreads) void sparse_adam_rows_kernel(AdamArgs
 // with its own learning rate) is merged on the host into one run whose step size switches at
 // split_col, so the buffer is read once in full rows instead of twice in strided blocks.  Same
 // arithmetic as adam_narrow, element for element.
-struct FlatAdamRun {
-    float *param;
-    const float *grad;
-    float *exp_avg;
-    float *exp_avg_sq;
-    int64_t n;         // floats
-    int row;           // floats per row (the column of element e is e % row)
-    int split_col;     // columns < split_col take step0, the rest step1 (row: one step size)
-    float step0, step1;
-    float bc2s;
-    int vec;           // all four arrays 16-B aligned and row % 4 == 0: float4 access
-};
-struct FlatAdamArgs {
-    FlatAdamRun r[kMaxGroups];
-    int64_t block_start[kMaxGroups + 1];
-    int n;
-};
-constexpr int kFlatPerThread = 8;  // two float4 per lane
-constexpr int64_t kFlatPerBlock = (int64_t)kAdamThreads * kFlatPerThread;
-
-__device__ __forceinline__ void flat_adam_one(const FlatAdamRun &R, float &p, float &m, float &v, float g, float ss,
-                                              float b1, float b2, float omb1, float omb2, float eps) {
-    const float mm = m * b1 + omb1 * g;
-    const float vv = v * b2 + omb2 * (g * g);
-    const float denom = sqrtf(vv) / R.bc2s + eps;
-    m = mm;
-    v = vv;
-    p = p + (-ss) * (mm / denom);
-}
-
+// FlatAdamRun, FlatAdamArgs and flat_adam_one (the per-element arithmetic): gsr_adam.h, shared with
+// post_step.hip's row-state kernel.
 __global__ __launch_bounds__(kAdamThreads) void dense_adam_flat_kernel(FlatAdamArgs a, float b1, float b2, float omb1,
                                                                        float omb2, float eps) {
     int k = 0;
@@ -310,6 +281,7 @@ __global__ __launch_bounds__(kAdamThreads) void dense_adam_flat_kernel(FlatAdamA
 // Builds the flat runs of a dense step.  A group that is a column block not pairing with its
 // neighbour into whole rows is left for the row-block kernel: its index goes to rest[].  Returns
 // the number of flat runs.
+}  // namespace
 int flat_adam_runs(int n_groups, const gsr_adam_group *groups, int64_t P, FlatAdamArgs &fa, int *rest,
                    int &n_rest) {
     std::memset(&fa, 0, sizeof(fa));
@@ -357,6 +329,7 @@ int flat_adam_runs(int n_groups, const gsr_adam_group *groups, int64_t P, FlatAd
     fa.block_start[fa.n] = blocks;
     return fa.n;
 }
+namespace {
 
 // The relevant rows compacted first (sparse steps: OurAdam's `relevant` rows, train_single.py:226).
 // The row-block kernel above launches a wave per (64 rows, group) -- P / 64 x groups waves, most of

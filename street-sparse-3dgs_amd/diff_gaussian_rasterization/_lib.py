@@ -48,6 +48,20 @@ class TrainStepArgs(ctypes.Structure):
                 ("depth_dens_weight", ctypes.c_double), ("skip_gaussian_step", _i), ("dense_rows", _i)]
 
 
+class PostStepArgs(ctypes.Structure):
+    """gsr_post_step_args (include/gsr_post.h)."""
+    _fields_ = [("N", _i64), ("n_nodes", _i64), ("M", _i), ("D", _i), ("skybox", _i64), ("width", _i), ("height", _i),
+                ("nodes", _vp), ("boxes", _vp),
+                ("xyz", _vp), ("features", _vp), ("opacity", _vp), ("scaling", _vp), ("rotation", _vp),
+                ("xyz_grad", _vp), ("features_grad", _vp), ("opacity_grad", _vp), ("scaling_grad", _vp),
+                ("rotation_grad", _vp), ("n_groups", _i), ("groups", ctypes.POINTER(AdamGroup)),
+                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("lock", _vp),
+                ("rebuild_live", _i), ("viewmatrix", _vp), ("projmatrix", _vp), ("campos", _vp),
+                ("campos_host", _f * 3), ("tan_fovx", _f), ("tan_fovy", _f), ("background", _vp), ("limit", _f),
+                ("gt", _vp), ("alpha_mask", _vp), ("exposure", _vp), ("lambda_dssim", ctypes.c_double),
+                ("losses", _vp), ("stream", _vp)]
+
+
 # exported symbol -> (restype, argtypes); must match include/gsr.h, gsr_train.h, gsr_hier.h, gsr_knn.h, gsr_densify.h
 SIGNATURES = {
     "gsr_rasterize_forward": (_i, [RESIZE_FN, RESIZE_FN, RESIZE_FN, _vp, _i, _i, _i, _vp, _i, _i,
@@ -281,6 +295,20 @@ STATION_SIGNATURES = {
     "gsr_station_stage_times_ms": (_i, [ctypes.POINTER(_f), _i]),
 }
 
+# include/gsr_post.h (the native post-optimisation iteration and its optimizer kernel).
+# New entry points only: the ABI version stays
+POST_SIGNATURES = {
+    "gsr_cut_mark_rows": (_i, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
+    "gsr_post_live_build": (_i, [_i, ctypes.POINTER(AdamGroup), _i64, _vp, _vp]),
+    "gsr_post_adam_step": (_i, [_i, ctypes.POINTER(AdamGroup), _i64, _vp, _i, _vp, _i64, _vp, ctypes.c_double,
+                                ctypes.c_double, ctypes.c_double, _vp]),
+    "gsr_post_ctx_create": (_vp, []),
+    "gsr_post_ctx_destroy": (None, [_vp]),
+    "gsr_post_ctx_stats": (_i, [_vp, ctypes.POINTER(_i64), _i]),
+    "gsr_post_ctx_read_rows": (_i, [_vp, _i, _vp, _i64, ctypes.POINTER(_i)]),
+    "gsr_post_step": (_i, [_vp, ctypes.POINTER(PostStepArgs), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+}
+
 ABI_VERSION = 7
 _lib = None
 
@@ -307,7 +335,8 @@ def load(path: str = LIB_PATH):
                               + list(LPIPS_SIGNATURES.items()) + list(MODEL_INIT_SIGNATURES.items())
                               + list(LIDAR_SIGNATURES.items()) + list(MESH_DEPTH_SIGNATURES.items())
                               + list(CHUNKER_SIGNATURES.items()) + list(VIEWS_SIGNATURES.items())
-                              + list(DEPTH_SCALE_SIGNATURES.items()) + list(STATION_SIGNATURES.items())):
+                              + list(DEPTH_SCALE_SIGNATURES.items()) + list(STATION_SIGNATURES.items())
+                              + list(POST_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -18,6 +18,9 @@
   model_init.create_from_cloud     a point cloud to a model, with or without a scaffold (create_from_pcd; csrc/model_init.hip)
   coarse.CoarseTrainStep / TrainCoarse  train_coarse.py's iteration and loop: the degree-1 scaffold
   scaffold.save_scaffold / load_scaffold  the scaffold's point_cloud.ply and pc_info.txt
+  post.PostTrainStep               one train_post.py iteration
+  native_post.NativePostStep       the same iteration as one native call (gsr_post_step; csrc/post_step.hip)
+  post_stage.TrainPost             train_post.py's loop, with load_hierarchy_model / save_hier / capture / restore
 """
 from .loss import l1_ssim, photo_loss  # noqa: F401
 from .optim import Adam  # noqa: F401
